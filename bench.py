@@ -23,8 +23,16 @@ Multi-GPU (BASELINE.json configs[4]), one process per GPU:
   With more ranks than visible GPUs (a rehearsal on a 1-GPU box) the ranks
   share the devices and the exchange runs over gloo; the line says so.
 
-Besides the headline, the default line carries secondary legs measured in the
-same run (each with its own barrier-bracketed timing, max over ranks):
+A plain run (`bench.py --gpus N --steps K --warmup W`) builds the problem,
+runs W untimed and K timed headline steps, writes the last timed step's
+outputs if --dump-outputs DIR is given (DIR/<name>.npy: cost, residuals,
+jacobian, ...; float64, arrays above DUMP_MAX_VALUES values as the fixed
+sample_indices elements; the inputs are the seeded generator's, identical from
+run to run) and prints the line.
+
+With --full the line also carries secondary legs measured in the same run
+after the headline (each with its own barrier-bracketed timing, max over
+ranks):
   gradient       residual+Jacobian+gradient J^T r (what the trust-region
                  minimizer requests, trust_region_minimizer.cc:242-255)
   same_point     the headline evaluation with new_evaluation_point = false
@@ -72,6 +80,8 @@ from ceres_amd import bal  # noqa: E402
 
 PEAK_HBM_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 METRIC = "residual+Jacobian evaluations/sec on BAL problem-13682; achieved HBM GB/s"
+DUMP_MAX_VALUES = 1 << 20  # --dump-outputs, per array: 8 MB of float64, at most 4 arrays a mode
+DUMP_SEED = 0xD0C5
 
 
 def parse():
@@ -105,8 +115,18 @@ def parse():
     ap.add_argument("--held-cameras", type=int, default=0,
                     help="hold the first K cameras constant (SetParameterBlockConstant, e.g. the "
                          "gauge): their blocks have no F cell (BlockSparseMatrix); not the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run the secondary legs and the CPU "
+                         "baseline (each with its own timing); a plain run sets up, warms up, times "
+                         "--steps steps and prints the line with `secondary` empty and "
+                         "`cpu_baseline` null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step of the headline left "
+                         "in its output buffers (rank 0's) as DIR/<name>.npy, float64; an array of "
+                         "more than DUMP_MAX_VALUES values is written as a fixed sample of its "
+                         "elements (sample_indices: they depend only on the array's length)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the gradient / residual-only / host-strip legs")
+                    help="with --full: skip the gradient / residual-only / host-strip legs")
     ap.add_argument("--secondary-steps", type=int, default=20)
     ap.add_argument("--settle", type=float, default=0.0,
                     help="seconds of untimed steps before the --warmup steps (default 0: the "
@@ -114,7 +134,8 @@ def parse():
                          "includes is documented in DESIGN.md section 5); reported as "
                          "settle_steps")
     ap.add_argument("--host-steps", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-only", action="store_true",
                     help="BASELINE.json configs[0]: problem-16 on the CPU ProgramEvaluator "
                          "restatement at num_threads=1 (no GPU); prints its own JSON line")
@@ -152,6 +173,28 @@ def launch_ranks(args):
            f"--nproc-per-node={args.gpus}", "--master-addr=127.0.0.1",
            f"--master-port={_free_port()}", os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.call(cmd)
+
+
+def sample_indices(n):
+    """The sorted element indices --dump-outputs keeps of an array of
+    n > DUMP_MAX_VALUES values: seeded, a function of n alone, so two builds
+    run with the same arguments write the same elements."""
+    rng = np.random.default_rng([DUMP_SEED, n])
+    return np.sort(rng.integers(0, n, size=DUMP_MAX_VALUES))
+
+
+def dump_outputs(path, outputs, rank):
+    """--dump-outputs: every device tensor of `outputs` (name -> tensor) as
+    path/<name>.npy in float64 (path/<name>.rank<r>.npy on a rank r > 0),
+    whole or as the sample_indices elements."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_VALUES:
+            t = t[torch.from_numpy(sample_indices(t.numel())).to(t.device)]
+        np.save(os.path.join(path, f"{name}{f'.rank{rank}' if rank else ''}.npy"),
+                t.cpu().numpy().astype(np.float64, copy=False))
 
 
 def make_loss(name):
@@ -437,8 +480,8 @@ def main():
                                       stream=stream, quaternion_manifold=quat,
                                       constant_cameras=tuple(range(args.held_cameras)))
     variant = quat or args.held_cameras > 0
-    if not (rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "jacobian"
-            and not variant):
+    if not (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+            and args.mode == "jacobian" and not variant):
         del arrays
         arrays = None
     build_s = time.perf_counter() - t_build
@@ -544,6 +587,24 @@ def main():
     settle = [0]
     elapsed, kernel_ms, kernel_ms_max = run_leg(step, args.steps, args.warmup, args.settle)
     settle_steps = settle[0]
+    if args.dump_outputs:  # before a later leg writes the same buffers
+        if args.mode == "jacobian":
+            last = (ring[0] - 1) % cost_ring.numel()  # the last timed step's cost slot
+            outputs = {"cost": cost_ring[last:last + 1], "residuals": se.residuals,
+                       "jacobian": se.jacobian}
+            if args.gradient:
+                outputs["gradient"] = se.gradient
+        elif args.mode == "residual":
+            outputs = {"cost": se.cost, "residuals": se.residuals}
+        elif args.mode == "candidate":
+            outputs = {"cost": se.cost, "candidate": cand}
+        elif args.mode == "spmv":
+            outputs = {"jp": jp, "jtjp": jtjp}
+        elif args.mode == "cgnr":
+            outputs = {"jtjp": jtjp}
+        else:
+            outputs = {"sy": sy}
+        dump_outputs(args.dump_outputs, outputs, rank)
     if args.mode in ("spmv", "cgnr", "schur"):  # no evaluate launches in the loop: the step time
         kernel_ms = kernel_ms_max = elapsed / args.steps * 1e3
 
@@ -577,7 +638,7 @@ def main():
 
     # ---- secondary legs --------------------------------------------------
     secondary = {}
-    if args.mode == "jacobian" and not args.no_secondary:
+    if args.full and args.mode == "jacobian" and not args.no_secondary:
         ks = args.secondary_steps
 
         def leg(name, fn, nbytes, steps, what):
@@ -755,7 +816,7 @@ def main():
                         "buffer; PCIe-inclusive, not the headline value)"}
             del bufs
 
-    if args.mode == "schur" and not args.no_secondary and world == 1:
+    if args.full and args.mode == "schur" and not args.no_secondary and world == 1:
         # One trust-region step's front end on the device, two ways
         # (VERDICT r5 #6): the evaluation writes the gradient (gradient_mode
         # 0, CameraGradientKernel) and cse_schur_init follows, or the
@@ -845,6 +906,7 @@ def main():
             "warmup": args.warmup,
             "settle_steps": settle_steps,
             "ms_per_step": elapsed / args.steps * 1e3,
+            "full": args.full,
             "higher_is_better": True,
             "scaling": args.scaling,
             "vs_baseline": None,

@@ -21,3 +21,18 @@ def test_cpu_only_line_is_configs0():
     assert line["n_gpus"] == 0 and line["value"] > 0
     assert line["config"]["blocks"] == 83718
     assert line["residual_only"]["value"] > line["value"]  # no Jets, no Jacobian stores
+
+
+def test_dump_sample_is_a_function_of_the_length():
+    """--dump-outputs: the elements kept of a large array (the headline's
+    695,703,456 Jacobian values) are fixed by its length, sorted, in range."""
+    import numpy as np
+
+    import bench
+    n = 24 * 28987644
+    idx = bench.sample_indices(n)
+    assert idx.shape == (bench.DUMP_MAX_VALUES,) and idx.dtype == np.int64
+    assert idx[0] >= 0 and idx[-1] < n and np.all(np.diff(idx) >= 0)
+    assert np.array_equal(idx, bench.sample_indices(n))
+    assert not np.array_equal(idx[:1000], bench.sample_indices(n + 1)[:1000])
+    assert 4 * 8 * bench.DUMP_MAX_VALUES <= 64 << 20  # at most 4 arrays a mode

@@ -6,7 +6,7 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 export CSE_BAL_CACHE=/tmp/cse_bal_cache
 TAG=${1:-r01}
-ARGS=${BENCH_ARGS:-"--no-cpu-baseline --steps 10 --warmup 2"}
+ARGS=${BENCH_ARGS:-"--full --no-cpu-baseline --steps 10 --warmup 2"}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || true

@@ -6,8 +6,8 @@
 #   TAG=r5a bash tools/gpu_run.sh \
 #     "tests tests/test_parity_gpu.py -k full_size" \
 #     "suite" \
-#     "bench" "bench --gradient --no-secondary" \
-#     "rocprof --no-cpu-baseline --steps 30 --warmup 3" \
+#     "bench --full" "bench --gradient" \
+#     "rocprof --full --no-cpu-baseline --steps 30 --warmup 3" \
 #     "rocprof-tests tests/test_parity_gpu.py -m slow" \
 #     "ab 3 jacobian plain:: jet::--jacobian-form=jet" \
 #     "configs" "pmc" "membench"
