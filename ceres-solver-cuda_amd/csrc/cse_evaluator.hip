@@ -1,9 +1,10 @@
 // cse_evaluator.hip -- the C ABI (include/cse.h) over the gfx950 kernels.
 //
-// Host side of the evaluator: validates and uploads the Program once
-// (RegisteredCUDAEvaluators::Init, internal/ceres/registered_cuda_evaluators.cc:226-280),
-// picks a layout policy per residual group, and runs one fused kernel per
-// group plus one finalize kernel per evaluation
+// Host side of the evaluator: uploads the Program once
+// (RegisteredCUDAEvaluators::Init, internal/ceres/registered_cuda_evaluators.cc:226-280)
+// as the host-only planner laid it out (plan.hpp: descriptor validation, the
+// layout policy of each residual group, its gradient plans and tables), and
+// runs one fused kernel per group plus one finalize kernel per evaluation
 // (RegisteredCUDAEvaluators::Evaluate, :46-103).
 //
 // The library reads no environment variable and has no build-time
@@ -29,18 +30,22 @@
 #include "jet_kernels.h"
 #include "launch.hpp"
 #include "multi_device.h"
+#include "plan.hpp"
 #include "schur_kernels.hpp"
 
 namespace cse {
-std::string& LastError();  // layout.cpp: one per thread, shared by every entry point
+std::string& LastError();  // layout.cpp: one per thread (cse_last_error reads it here)
 }  // namespace cse
 
 namespace {
 
-int Fail(int code, const std::string& msg) {
-  cse::LastError() = msg;
-  return code;
-}
+using cse::kAffineCrs;
+using cse::kAffinePacked;
+using cse::kKindQuaternionTangent;
+using cse::kTable;
+using cse::KindShape;
+
+int Fail(int code, const std::string& msg) { return CseFail(code, msg); }
 
 // Entry points whose arguments are device pointers of one device.
 #define CSE_SINGLE_DEVICE(ev, what)                                                         \
@@ -66,11 +71,8 @@ using TestLinear2_23 = cse::LinearTestKind<2, 2, 3>;
 using TestLinear3_24 = cse::LinearTestKind<3, 2, 4>;
 using TestLinear4_34 = cse::LinearTestKind<4, 3, 4>;
 
-// Internal kernel kinds (never in a descriptor): a group whose slot-0
-// blocks carry a manifold the affine kernels build in registers.
-constexpr int kKindQuaternionTangent = -100;  // SNAVELY_QUATERNION_2_10_3, slot 0 on
-                                              // CSE_MANIFOLD_QUATERNION_EUCLIDEAN
-
+// (kKindQuaternionTangent, plan.hpp: the internal kernel kind of a group
+// whose slot-0 blocks are on CSE_MANIFOLD_QUATERNION_EUCLIDEAN.)
 template <class F>
 bool VisitKind(int kind, F&& f) {
   switch (kind) {
@@ -91,8 +93,33 @@ bool VisitKind(int kind, F&& f) {
   }
 }
 
-// Known-answer-test kinds: general path and trivial loss only.
-bool IsTestKind(int kind) { return kind >= 100 && kind < CSE_FUNCTOR_USER_FIRST; }
+// The planner's shape table (plan.hpp, cse::kKindRows) row by row against
+// the functor types the kernels are instantiated with.
+template <class K>
+constexpr bool KindRowMatches(int kind) {
+  using Tr = cse::KindTraits<K>;
+  const cse::KindRow* r = cse::KindRowOf(kind);
+  if (!r || r->nr != Tr::NR || r->nb != Tr::NB || r->data != Tr::D || r->x0 != Tr::X0) return false;
+  for (int j = 0; j < cse::kMaxSlots; ++j)
+    if (r->sz[j] != (j < Tr::NB ? K::kSizes[j] : 0)) return false;
+  return true;
+}
+#define CSE_KIND_ROW(kind, K) static_assert(KindRowMatches<K>(kind), "plan.hpp: kKindRows row of " #kind)
+CSE_KIND_ROW(kKindQuaternionTangent, cse::SnavelyQuaternionTangentKind);
+CSE_KIND_ROW(CSE_FUNCTOR_SNAVELY_2_9_3, cse::SnavelyKind);
+CSE_KIND_ROW(CSE_FUNCTOR_SNAVELY_NO_DISTORTION_2_7_3, cse::SnavelyNoDistortionKind);
+CSE_KIND_ROW(CSE_FUNCTOR_SNAVELY_QUATERNION_2_10_3, cse::SnavelyQuaternionKind);
+CSE_KIND_ROW(CSE_FUNCTOR_POINT_DISPLACEMENT_3_3, cse::PointDisplacementKind);
+CSE_KIND_ROW(CSE_FUNCTOR_TEST_LINEAR_3_2_3_4, TestLinear3_234);
+CSE_KIND_ROW(CSE_FUNCTOR_TEST_LINEAR_3_4_3_2, TestLinear3_432);
+CSE_KIND_ROW(CSE_FUNCTOR_TEST_LINEAR_2_2_3, TestLinear2_23);
+CSE_KIND_ROW(CSE_FUNCTOR_TEST_LINEAR_3_2_4, TestLinear3_24);
+CSE_KIND_ROW(CSE_FUNCTOR_TEST_LINEAR_4_3_4, TestLinear4_34);
+CSE_KIND_ROW(CSE_FUNCTOR_TEST_BILINEAR_1_2_2, cse::BilinearTestKind);
+CSE_KIND_ROW(CSE_FUNCTOR_TEST_TEN_PARAMETER_1_x10, cse::TenParameterTestKind);
+CSE_KIND_ROW(CSE_FUNCTOR_TEST_PARTIAL_OUTPUT_2_1, cse::PartialOutputTestKind);
+#undef CSE_KIND_ROW
+static_assert(sizeof(cse::kKindRows) / sizeof(cse::kKindRows[0]) == 13, "one assert per kKindRows row");
 
 // ---- User functor kinds (cse_register_functor): the kernels live in the
 // user's TU (include/ceres_amd/autodiff_cuda.h); the library holds their
@@ -113,47 +140,21 @@ const cse_functor_ops* UserOps(int kind) {
 
 bool IsUserKind(int kind) { return UserOps(kind) != nullptr; }
 
-// Every affine kernel of a user kind present (the header builds all eight
-// or none).
-bool UserAffine(const cse_functor_ops* u) {
-  bool all = true;
-  for (int c = 0; c < 2; ++c)
-    for (int j = 0; j < 2; ++j)
-      for (int d = 0; d < 2; ++d) all = all && u->affine[c][j][d] != nullptr;
-  return all;
+}  // namespace
+
+// A registered user kind's launch table and name (cse::UserLookup).
+const cse_functor_ops* CseUserKind(int kind, std::string* name) {
+  if (kind < CSE_FUNCTOR_USER_FIRST) return nullptr;
+  std::lock_guard<std::mutex> lock(g_user_mu);
+  const size_t i = (size_t)(kind - CSE_FUNCTOR_USER_FIRST);
+  if (i >= g_user_kinds.size()) return nullptr;
+  *name = g_user_kinds[i]->name;
+  return &g_user_kinds[i]->ops;
 }
 
-struct KindShape {
-  int nr = 0, nb = 0, data = 0;
-  int sz[cse::kMaxSlots] = {};
-  int s0 = 0, s1 = 0;  // sz[0], sz[1] (0 if absent): the two-slot affine path
-  int x0 = 0;          // slot-0 values gathered (ambient; s0 is the Jacobian's columns)
-};
+namespace {
 
-bool ShapeOf(int kind, KindShape* k) {
-  if (const cse_functor_ops* u = UserOps(kind)) {
-    *k = KindShape{};
-    k->nr = u->num_residuals;
-    k->nb = u->num_parameter_blocks;
-    k->data = u->data_size;
-    for (int j = 0; j < k->nb; ++j) k->sz[j] = u->parameter_block_sizes[j];
-    k->s0 = k->sz[0];
-    k->s1 = k->nb > 1 ? k->sz[1] : 0;
-    k->x0 = k->s0;
-    return true;
-  }
-  return VisitKind(kind, [&](auto kd) {
-    using K = decltype(kd);
-    using Tr = cse::KindTraits<K>;
-    k->nr = Tr::NR;
-    k->nb = Tr::NB;
-    k->data = Tr::D;
-    for (int j = 0; j < Tr::NB; ++j) k->sz[j] = K::kSizes[j];
-    k->s0 = k->sz[0];
-    k->s1 = Tr::NB > 1 ? k->sz[1] : 0;
-    k->x0 = Tr::X0;
-  });
-}
+bool ShapeOf(int kind, KindShape* k) { return cse::ShapeOf(kind, UserOps(kind), k); }
 
 // Device buffer, move-only, freed on destruction.
 template <typename T>
@@ -202,89 +203,41 @@ struct DevBuf {
   }
 };
 
-struct Group {
-  int kind = 0;
-  const cse_functor_ops* user = nullptr;  // a registered user functor kind
+// A residual group on the device: the planner's decisions (cse::GroupPlan,
+// plan.hpp) and the buffers its tables were uploaded to.
+struct Group : cse::GroupPlan {
   std::string user_name;
-  KindShape shape{};
-  cse_loss loss{};
-  int64_t n = 0;
-  bool affine = false;
-  int policy = 0;
-  int64_t partial_offset = 0;
-  int64_t num_wg = 0;
   DevBuf<int32_t> ids;
   DevBuf<double> data;
   DevBuf<int64_t> gindex;  // only when not contiguous
-  int64_t first = 0;
-  // affine parameters
-  int64_t state_base[2] = {0, 0};
-  int64_t delta_base[2] = {0, 0};
-  int64_t res_base = 0;
-  int64_t jac_base[2][3] = {{0, 0, 0}, {0, 0, 0}};
-  int64_t jac_stride[2] = {0, 0};
-  // Repacked slot-0 table (affine path, small id ranges).
-  int32_t slot0_lo = 0;
-  int64_t slot0_count = 0;
-  int slot0_stride = 0;
-  int packed_stride = 0;  // row stride of the repacked slot-0 table (doubles)
-  // The manifold DetectAffine chose for slot 0, taken from the first block
-  // with an active slot 0 (held blocks carry no Jacobian columns, so their
-  // own manifold does not matter).
-  int slot0_manifold = CSE_MANIFOLD_MATRIX;
-  DevBuf<double> packed0;
-  // Gradient post-pass plan per slot (affine groups with a Jacobian layout).
-  struct GradPlan {
-    bool ready = false;
-    bool wave = false;  // one wave (not one lane) per parameter block
-    int32_t lo = 0;
-    int64_t count = 0;
+  DevBuf<double> packed0;  // repacked slot-0 table (repack0)
+  // Gradient post-pass plan per slot (cse::GradPlanInfo, cse::GradTables).
+  struct GradPlan : cse::GradPlanInfo {
     DevBuf<int32_t> perm;  // empty = identity
     DevBuf<int64_t> off;
-    // wave mode: chunks of at most cse::kGradChunk blocks
     DevBuf<int64_t> chunk_begin, chunk_off;
-    DevBuf<int32_t> chunk_pb;  // parameter block (id) of each chunk
-    DevBuf<int32_t> chunk_order;  // passes > 1: the chunks pass-major (BuildGradPlan)
-    int passes = 1;
+    DevBuf<int32_t> chunk_pb;
+    DevBuf<int32_t> chunk_order;
     DevBuf<double> chunk_partial;
-    int64_t nchunks = 0;
-    int64_t nperm = 0;  // blocks in the plan (all but those with a constant block)
-    bool all_present = false;  // every id in [lo, lo + count) has a block
   } grad[2];
-  // Gradient mode 0 writes every gradient row exactly once (grad_exact): one
-  // group, no constant blocks, every camera and point id of its ranges
-  // present and their rows tiling the effective parameters.  Then the tail
-  // kernels assign instead of adding and the gradient is not zeroed first.
-  bool grad_exact = false;
-  // Constant slot-0 blocks on the affine path (BlockSparseMatrix): the
-  // active-bit table over the slot-0 id range, each id's repack source
-  // (state offset, or -1 - constant-state offset), and per 64-block chunk
-  // the offset of its first F cell.
-  bool const0 = false;
+  // const0 (cse::GroupTables): the active bits, repack sources, delta
+  // offsets and per-chunk first cells.
   DevBuf<uint32_t> act0;
   DevBuf<int64_t> src0, fbase, delta0;
-  std::vector<int64_t> h_fbase;
   // Held-camera sectors (HeldSectorFixupKernel): each chunk's two side
   // slots and the previous chunk with F cells (BSM) or row blocks (CRS).
   DevBuf<double> side;
   DevBuf<int32_t> prev_seg;
-  // Fused gradient (cse::FusedGrad): eligible groups, and their slot-1
-  // boundary entries and slot-0 contributions (allocated on first use).
-  bool fuse_ok = false;
+  // Fused gradient (cse::FusedGrad): the slot-1 boundary entries and slot-0
+  // contributions of eligible groups (allocated on first use).
   DevBuf<double> gside, gcontrib;
-  // cse_options.jacobian_form = CSE_JACOBIAN_JET on a Snavely group: its
-  // Jacobian kernels are the Jet<double, 12> instantiations (jet_kernels.h).
-  bool jet = false;
   // Slot-0-sorted functor data and slot-1 ids (CameraGradientKernel; built
   // on first use).
   DevBuf<double> sdata;
   DevBuf<int32_t> sid1;
   bool sorted_ready = false;
-  // Table policy: each 64-block chunk's store runs (BuildTableRuns), and
-  // slot 0 plain in every block (DetectPlain0).
+  // Table policy: each 64-block chunk's store runs.
   DevBuf<int64_t> runs;
-  bool plain0 = false;
-  int64_t plain0_state_base = 0, plain0_delta_base = 0;
 };
 
 using LaunchFn = void (*)(const cse::GroupArgs&, int64_t num_wg, hipStream_t);
@@ -300,10 +253,6 @@ constexpr int kOperatorWavesPerWg = cse::kWavesPerBlock;
 // (ReduceFinalizeKernel); below, one FinalizeKernel.
 constexpr int64_t kPartialsTwoPass = 4096;
 constexpr int kPartialBlocks = 128;
-
-// Layout policy of a group: 0 = table, 1 = affine packed cells (BSM),
-// 2 = affine interleaved rows (CRS).
-enum Policy { kTable = 0, kAffinePacked = 1, kAffineCrs = 2 };
 
 template <class K, int L, bool J>
 void LaunchTable(const cse::GroupArgs& a, int64_t num_wg, hipStream_t s) {
@@ -363,19 +312,9 @@ void LaunchFusedPoints(const cse::GroupArgs& a, int64_t num_wg, hipStream_t s) {
                      dim3(cse::kWave), 0, s, a);
 }
 
-// Kinds with the fused gradient: the Snavely camera and the quaternion
-// camera on its manifold (the same 2 x (9 + 3) Jacobian shape).
-bool FusedKind(int kind) {
-  return kind == CSE_FUNCTOR_SNAVELY_2_9_3 || kind == kKindQuaternionTangent;
-}
-
-// The Jacobian operators built for the Snavely shape (CgnrMultiplyKernel,
-// the Schur kernels) read only the Jacobian's values, so they serve every
-// fused-gradient group of that shape -- 2 residuals, blocks of 9 (tangent)
-// and 3 -- the library's kinds and user kinds alike.
-bool SnavelyShaped(const Group& G) {
-  return G.shape.nb == 2 && G.shape.nr == 2 && G.shape.s0 == 9 && G.shape.s1 == 3;
-}
+using cse::FusedKind;
+bool SnavelyShaped(const Group& G) { return cse::SnavelyShaped(G.shape); }
+bool UserFused(const Group& G) { return cse::UserFused(G.user, G.shape); }
 
 // f(std::integral_constant<int, s0>) for the slot-0 sizes the fused
 // gradient's tail is built for (1..16, the affine kernels' bound).
@@ -392,42 +331,34 @@ bool VisitSlot0Size(int s0, F&& f) {
   }
 }
 
-// User kinds that registered the fused gradient's launches (cse_functor_ops
-// ABI 5: two slots, slot 1 of 3 parameters): gradient_mode 0's form only
-// (points kernel, CameraGradientKernel, the tail); the other modes, the Jet
-// form and the operators stay with the library's kinds.
-bool UserFused(const Group& G) {
-  return G.user && G.user->fused_points[0] && G.user->fused_points[1] && G.user->camera_gradient &&
-         G.shape.nb == 2 && G.shape.s1 == 3 && G.shape.s0 >= 1 && G.shape.s0 <= 16;
+// f(std::integral_constant<int, L>) with the kernels' loss template argument
+// of a cse_loss kind: Huber, Cauchy, and the trivial loss for every other.
+template <class F>
+auto VisitLoss(int loss, F&& f) {
+  switch (loss) {
+    case CSE_LOSS_HUBER: return f(std::integral_constant<int, cse::kLossHuber>{});
+    case CSE_LOSS_CAUCHY: return f(std::integral_constant<int, cse::kLossCauchy>{});
+    default: return f(std::integral_constant<int, cse::kLossTrivial>{});
+  }
 }
 
 template <class K>
 LaunchFn PickFusedK(int loss, bool crs, bool points) {
-  switch (loss) {
-    case CSE_LOSS_HUBER:
-      return points ? (crs ? &LaunchFusedPoints<K, cse::kLossHuber, true> : &LaunchFusedPoints<K, cse::kLossHuber, false>)
-                    : (crs ? &LaunchFused<K, cse::kLossHuber, true> : &LaunchFused<K, cse::kLossHuber, false>);
-    case CSE_LOSS_CAUCHY:
-      return points ? (crs ? &LaunchFusedPoints<K, cse::kLossCauchy, true> : &LaunchFusedPoints<K, cse::kLossCauchy, false>)
-                    : (crs ? &LaunchFused<K, cse::kLossCauchy, true> : &LaunchFused<K, cse::kLossCauchy, false>);
-    default:
-      return points ? (crs ? &LaunchFusedPoints<K, cse::kLossTrivial, true> : &LaunchFusedPoints<K, cse::kLossTrivial, false>)
-                    : (crs ? &LaunchFused<K, cse::kLossTrivial, true> : &LaunchFused<K, cse::kLossTrivial, false>);
-  }
+  return VisitLoss(loss, [&](auto l) -> LaunchFn {
+    constexpr int L = decltype(l)::value;
+    return points ? (crs ? &LaunchFusedPoints<K, L, true> : &LaunchFusedPoints<K, L, false>)
+                  : (crs ? &LaunchFused<K, L, true> : &LaunchFused<K, L, false>);
+  });
 }
 
 template <class K, bool Crs>
 LaunchFn PickFusedC0(int loss, bool points) {
   using TP = cse::PointsOnlyTuneC0;
   using TF = cse::ShippedTuneC0;
-  switch (loss) {
-    case CSE_LOSS_HUBER:
-      return points ? &LaunchFusedPoints<K, cse::kLossHuber, Crs, TP> : &LaunchFused<K, cse::kLossHuber, Crs, TF>;
-    case CSE_LOSS_CAUCHY:
-      return points ? &LaunchFusedPoints<K, cse::kLossCauchy, Crs, TP> : &LaunchFused<K, cse::kLossCauchy, Crs, TF>;
-    default:
-      return points ? &LaunchFusedPoints<K, cse::kLossTrivial, Crs, TP> : &LaunchFused<K, cse::kLossTrivial, Crs, TF>;
-  }
+  return VisitLoss(loss, [&](auto l) -> LaunchFn {
+    constexpr int L = decltype(l)::value;
+    return points ? &LaunchFusedPoints<K, L, Crs, TP> : &LaunchFused<K, L, Crs, TF>;
+  });
 }
 
 // points = true: the slot-1 rows only (gradient_mode 0, slot 0 from
@@ -475,7 +406,6 @@ LaunchFn PickJP(bool jac, int policy, bool dma) {
   return jac ? &LaunchTable<K, L, true> : &LaunchTable<K, L, false>;
 }
 
-
 // const0: the group has constant slot-0 blocks (FusedKind kinds, the
 // repacked table; DetectAffine): the Jacobian kernel with the packed F cells
 // (BSM) or the packed row blocks of two widths (CRS).
@@ -484,18 +414,10 @@ LaunchFn PickConst0(int kind, int loss, bool jac, bool crs) {
     using K = decltype(kd);
     using T = cse::ShippedTuneC0;
     if (!jac) return nullptr;  // residual/cost kernels write no Jacobian: the usual ones
-    if (crs) {
-      switch (loss) {
-        case CSE_LOSS_HUBER: return &LaunchTwoRoundCrs<K, cse::kLossHuber, 2, T>;
-        case CSE_LOSS_CAUCHY: return &LaunchTwoRoundCrs<K, cse::kLossCauchy, 2, T>;
-        default: return &LaunchTwoRoundCrs<K, cse::kLossTrivial, 2, T>;
-      }
-    }
-    switch (loss) {
-      case CSE_LOSS_HUBER: return &LaunchTwoRound<K, cse::kLossHuber, 2, T>;
-      case CSE_LOSS_CAUCHY: return &LaunchTwoRound<K, cse::kLossCauchy, 2, T>;
-      default: return &LaunchTwoRound<K, cse::kLossTrivial, 2, T>;
-    }
+    return VisitLoss(loss, [&](auto l) -> LaunchFn {
+      constexpr int L = decltype(l)::value;
+      return crs ? &LaunchTwoRoundCrs<K, L, 2, T> : &LaunchTwoRound<K, L, 2, T>;
+    });
   };
   if (kind == kKindQuaternionTangent) return pick(cse::SnavelyQuaternionTangentKind{});
   if (kind == CSE_FUNCTOR_SNAVELY_2_9_3) return pick(cse::SnavelyKind{});
@@ -511,40 +433,22 @@ LaunchFn Pick(int kind, int loss, bool jac, int policy, bool dma, bool const0 = 
   VisitKind(kind, [&](auto kd) {
     using K = decltype(kd);
     if constexpr (cse::AffineOnly<K>::value) {
-      if (policy == kAffinePacked || policy == kAffineCrs) {
-        const bool crs = policy == kAffineCrs;
-        switch (loss) {
-          case CSE_LOSS_HUBER: fn = crs ? PickAffine<K, cse::kLossHuber, true>(jac, dma) : PickAffine<K, cse::kLossHuber, false>(jac, dma); break;
-          case CSE_LOSS_CAUCHY: fn = crs ? PickAffine<K, cse::kLossCauchy, true>(jac, dma) : PickAffine<K, cse::kLossCauchy, false>(jac, dma); break;
-          default: fn = crs ? PickAffine<K, cse::kLossTrivial, true>(jac, dma) : PickAffine<K, cse::kLossTrivial, false>(jac, dma); break;
-        }
-      }
+      if (policy == kAffinePacked || policy == kAffineCrs)
+        fn = VisitLoss(loss, [&](auto l) -> LaunchFn {
+          constexpr int L = decltype(l)::value;
+          return policy == kAffineCrs ? PickAffine<K, L, true>(jac, dma) : PickAffine<K, L, false>(jac, dma);
+        });
     } else if constexpr (cse::TestOnly<K>::value) {
       if (loss == CSE_LOSS_TRIVIAL)
         fn = jac ? &LaunchTable<K, cse::kLossTrivial, true> : &LaunchTable<K, cse::kLossTrivial, false>;
     } else {
-      switch (loss) {
-        case CSE_LOSS_HUBER: fn = PickJP<K, cse::kLossHuber>(jac, policy, dma); break;
-        case CSE_LOSS_CAUCHY: fn = PickJP<K, cse::kLossCauchy>(jac, policy, dma); break;
-        default: fn = PickJP<K, cse::kLossTrivial>(jac, policy, dma); break;
-      }
+      fn = VisitLoss(loss, [&](auto l) -> LaunchFn { return PickJP<K, decltype(l)::value>(jac, policy, dma); });
     }
   });
   return fn;
 }
 
 }  // namespace
-
-int CseFail(int code, const std::string& msg) { return Fail(code, msg); }
-
-bool CseKindShape(int kind, int* num_residuals, int* num_blocks, int* data_size) {
-  KindShape k;
-  if (!ShapeOf(kind, &k)) return false;
-  *num_residuals = k.nr;
-  *num_blocks = k.nb;
-  *data_size = k.data;
-  return true;
-}
 
 struct cse_evaluator {
   // A multi-device evaluator (cse_create_multi) is a shell around CseMulti;
@@ -594,12 +498,7 @@ struct cse_evaluator {
   int64_t launches = 0;
   // The implicit Schur complement (cse_schur_*): structure found at create
   // time, values and vectors bound by cse_schur_init.
-  struct Schur {
-    bool eligible = false;
-    bool duplicates = false;  // an e block sees one f block twice
-    int64_t e_cols = 0, f_cols = 0;
-    int64_t f_col_base = 0;   // f index of camera id = f_col_base + 9 id
-    int64_t nchunks = 0, nbig = 0;
+  struct Schur : cse::SchurPlan {
     DevBuf<int64_t> chunk_begin, big;
     DevBuf<double> ete_inv, precond, partial, ub;
     bool ready = false;
@@ -610,174 +509,6 @@ struct cse_evaluator {
 
 namespace {
 
-int Validate(const cse_problem_desc* d) {
-  if (!d) return Fail(CSE_ERR_INVALID, "null descriptor");
-  if (d->abi_version != CSE_ABI_VERSION)
-    return Fail(CSE_ERR_INVALID, "abi_version mismatch: descriptor " +
-                                     std::to_string(d->abi_version) + ", library " +
-                                     std::to_string(CSE_ABI_VERSION));
-  if (d->num_groups < 0 || (d->num_groups > 0 && !d->groups))
-    return Fail(CSE_ERR_INVALID, "bad groups");
-  if (d->num_parameter_blocks < 0 || (d->num_parameter_blocks > 0 && !d->parameter_blocks))
-    return Fail(CSE_ERR_INVALID, "bad parameter blocks");
-  for (int64_t b = 0; b < d->num_parameter_blocks; ++b) {
-    const cse_parameter_block& pb = d->parameter_blocks[b];
-    if (pb.size <= 0 || pb.tangent_size < 0 || pb.tangent_size > pb.size)
-      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) + " has bad size");
-    const int64_t lim = pb.is_constant ? d->num_constant_parameters : d->num_parameters;
-    if (pb.state_offset < 0 || pb.state_offset + pb.size > lim)
-      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) + " state out of range");
-    if (!pb.is_constant && (pb.delta_offset < 0 ||
-                            pb.delta_offset + pb.tangent_size > d->num_effective_parameters))
-      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) + " delta out of range");
-    if (pb.plus_jacobian_offset >= 0 &&
-        pb.plus_jacobian_offset + (int64_t)pb.size * pb.tangent_size > d->num_plus_jacobian_values)
-      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) +
-                                       " plus jacobian out of range");
-    if (pb.manifold != CSE_MANIFOLD_MATRIX && pb.manifold != CSE_MANIFOLD_QUATERNION_EUCLIDEAN)
-      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) + ": unknown manifold " +
-                                       std::to_string(pb.manifold));
-    if (pb.manifold == CSE_MANIFOLD_QUATERNION_EUCLIDEAN &&
-        (pb.size < 4 || pb.tangent_size != pb.size - 1 || pb.plus_jacobian_offset >= 0))
-      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) +
-                                       ": the quaternion manifold needs size >= 4, tangent_size "
-                                       "size - 1 and plus_jacobian_offset -1");
-  }
-  if (d->num_constant_parameters > 0 && !d->constant_state)
-    return Fail(CSE_ERR_INVALID, "constant_state missing");
-  if (d->num_plus_jacobian_values > 0 && !d->plus_jacobians)
-    return Fail(CSE_ERR_INVALID, "plus_jacobians missing");
-  if (d->num_residual_blocks < 0 || !d->residual_layout)
-    return Fail(CSE_ERR_INVALID, "residual_layout missing");
-  return CSE_OK;
-}
-
-// Is the group table-free?  Returns the Policy (see evaluate_kernel.hpp
-// for the two affine shapes).
-// CameraGradientKernel's passes: its point gathers (slot 1, a table of
-// 8 s1 bytes per point) hit the Infinity Cache only while the table plus
-// every byte streamed between two uses of a line fits in ~256 MiB
-// (MI355X_MICROARCH.md, Infinity Cache).  In camera order a point's blocks
-// are spread over the whole launch, between which the sorted functor data
-// and slot-1 ids (8 data + 4 bytes a block) stream by: 107 + 580 MB at
-// problem-13682.  Cut into passes of consecutive point ranges, taken one
-// after the other, each pass touches 1/passes of both: passes = the total
-// over kCamGradPassBytes, at most 64.  (Passes 8 times finer dealt to the
-// XCDs measured no faster.)  The camera sums over written contributions
-// (gradient_mode 3, the Schur and CGNR operators' F^T u) take the same
-// plan's chunks pass-major too (GradientContribKernel's order).
-constexpr double kCamGradPassBytes = 96e6;
-int CamGradPasses(const cse_residual_group& g, const KindShape& k) {
-  int32_t lo = INT32_MAX, hi = INT32_MIN;
-  for (int64_t i = 0; i < g.num_blocks; ++i) {
-    lo = std::min(lo, g.parameter_block_ids[i * k.nb + 1]);
-    hi = std::max(hi, g.parameter_block_ids[i * k.nb + 1]);
-  }
-  if (g.num_blocks == 0) return 1;
-  const double bytes = 8.0 * k.s1 * ((double)hi - lo + 1) + (8.0 * k.data + 4.0) * g.num_blocks;
-  const int p = (int)std::ceil(bytes / kCamGradPassBytes);
-  return std::max(1, std::min(64, p));
-}
-
-// Blocks of slot j listed per parameter block (stable counting sort): the
-// gradient post-pass sums each parameter block's blocks in this order.
-// cpb (may be null): the descriptor's parameter blocks; blocks whose slot-j
-// parameter block is constant are left out (a held camera has no gradient
-// row), which makes the plan a permutation of the other blocks only.
-// passes > 1 (slot 0 of a two-slot kind): each parameter block's list is
-// further ordered by pass, pass(i) = i * passes / n (block order: in a
-// Schur-ordered problem, consecutive point ranges), and no chunk straddles
-// two passes; chunk_order lists the chunks pass-major, the order in which
-// CameraGradientKernel takes them (CamGradPasses).
-int BuildGradPlan(const cse_residual_group& g, const KindShape& k, int j, Group::GradPlan* plan,
-                  hipStream_t s, const cse_parameter_block* cpb = nullptr, int passes = 1) {
-  const int64_t n = g.num_blocks;
-  if (passes < 1 || n < passes) passes = 1;
-  auto skip = [&](int64_t i) {
-    return cpb && cpb[g.parameter_block_ids[i * k.nb + j]].is_constant;
-  };
-  auto pass_of = [&](int64_t i) { return (int)((__int128)i * passes / n); };
-  int32_t lo = g.parameter_block_ids[j], hi = lo;
-  for (int64_t i = 0; i < n; ++i) {
-    lo = std::min(lo, g.parameter_block_ids[i * k.nb + j]);
-    hi = std::max(hi, g.parameter_block_ids[i * k.nb + j]);
-  }
-  const int64_t count = (int64_t)hi - lo + 1;
-  // Counting sort on (parameter block, pass): poff[p * passes + t].
-  std::vector<int64_t> poff(count * passes + 1, 0);
-  bool sorted = true;
-  int64_t kept = 0, prev = INT64_MIN;
-  for (int64_t i = 0; i < n; ++i) {
-    if (skip(i)) {
-      sorted = false;  // a permutation of the kept blocks, never the identity
-      continue;
-    }
-    const int32_t id = g.parameter_block_ids[i * k.nb + j];
-    ++poff[(id - lo) * passes + pass_of(i) + 1];
-    if (id < prev) sorted = false;
-    prev = id;
-    ++kept;
-  }
-  plan->nperm = kept;
-  for (int64_t p = 0; p < count * passes; ++p) poff[p + 1] += poff[p];
-  std::vector<int64_t> off(count + 1);
-  for (int64_t p = 0; p <= count; ++p) off[p] = poff[p * passes];
-  plan->all_present = true;
-  for (int64_t p = 0; p < count && plan->all_present; ++p) plan->all_present = off[p + 1] > off[p];
-  int rc;
-  if (!sorted) {
-    std::vector<int32_t> perm(std::max<int64_t>(kept, 1));
-    std::vector<int64_t> next(poff.begin(), poff.end() - 1);
-    for (int64_t i = 0; i < n; ++i)
-      if (!skip(i))
-        perm[next[(g.parameter_block_ids[i * k.nb + j] - lo) * passes + pass_of(i)]++] = (int32_t)i;
-    if ((rc = plan->perm.upload(perm.data(), perm.size(), s))) return rc;
-    if (hipStreamSynchronize(s) != hipSuccess) return Fail(CSE_ERR_HIP, "hipStreamSynchronize failed");
-  }
-  if ((rc = plan->off.upload(off.data(), off.size(), s))) return rc;
-  if (hipStreamSynchronize(s) != hipSuccess) return Fail(CSE_ERR_HIP, "hipStreamSynchronize failed");
-  plan->lo = lo;
-  plan->count = count;
-  plan->wave = !sorted && n >= 32 * count;  // on average 32+ blocks per parameter block
-  // Chunks: the wave-mode post-pass and the fused gradient's slot-0 pass.
-  if (!sorted) {
-    std::vector<int64_t> begin, coff(count + 1, 0);
-    std::vector<int32_t> cpb, cpass;
-    for (int64_t p = 0; p < count; ++p) {
-      coff[p] = (int64_t)begin.size();
-      for (int t = 0; t < passes; ++t)
-        for (int64_t q = poff[p * passes + t]; q < poff[p * passes + t + 1]; q += cse::kGradChunk) {
-          begin.push_back(q);
-          cpb.push_back((int32_t)(lo + p));
-          cpass.push_back(t);
-        }
-    }
-    coff[count] = (int64_t)begin.size();
-    plan->nchunks = (int64_t)begin.size();
-    plan->passes = passes;
-    if (passes > 1) {  // pass-major launch order, camera order within a pass
-      std::vector<int32_t> order;
-      order.reserve(begin.size());
-      for (int t = 0; t < passes; ++t)
-        for (int64_t c = 0; c < plan->nchunks; ++c)
-          if (cpass[c] == t) order.push_back((int32_t)c);
-      if ((rc = plan->chunk_order.upload(order.data(), order.size(), s))) return rc;
-    }
-    // Chunk c covers [begin[c], begin[c + 1]): a parameter block's last
-    // chunk ends at off[p + 1], where the next non-empty one starts.
-    begin.push_back(kept);
-    if ((rc = plan->chunk_begin.upload(begin.data(), begin.size(), s))) return rc;
-    if ((rc = plan->chunk_off.upload(coff.data(), coff.size(), s))) return rc;
-    if (!cpb.empty() && (rc = plan->chunk_pb.upload(cpb.data(), cpb.size(), s))) return rc;
-    const int size = j == 0 ? k.s0 : k.s1;
-    if ((rc = plan->chunk_partial.alloc((size_t)std::max<int64_t>(1, plan->nchunks) * size)))
-      return rc;
-    if (hipStreamSynchronize(s) != hipSuccess) return Fail(CSE_ERR_HIP, "hipStreamSynchronize failed");
-  }
-  plan->ready = true;
-  return CSE_OK;
-}
-
 // The post-pass form of a plan (cse::GradForm) and its chunk table.
 int GradFormOf(const cse::GradArgs& ga, const Group::GradPlan& P) {
   if (ga.perm == nullptr) return cse::kGradRange;  // identity order: contiguous ranges (points)
@@ -787,13 +518,8 @@ cse::GradChunks GradChunksOf(const Group::GradPlan& P) {
   return cse::GradChunks{P.chunk_begin.p, P.chunk_off.p, P.chunk_partial.p, P.nchunks};
 }
 
-// Gradient post-pass kernels of the built-in shapes; a user kind brings its
-// own (cse_functor_ops.gradient).
-bool GradSupported(int nr, int size, const cse_functor_ops* user = nullptr, int slot = 0) {
-  if (user) return user->gradient[slot] != nullptr;
-  return (nr == 2 && (size == 9 || size == 3 || size == 7 || size == 10)) || (nr == 3 && size == 3);
-}
-
+// The post-pass kernels of the built-in shapes (the planner's GradSupported
+// names the same ones); a user kind brings its own (cse_functor_ops.gradient).
 bool LaunchGradPass(int nr, int size, const cse::GradArgs& ga, const Group::GradPlan& P,
                     hipStream_t s, const cse_functor_ops* user = nullptr, int slot = 0) {
   const int form = GradFormOf(ga, P);
@@ -809,213 +535,6 @@ bool LaunchGradPass(int nr, int size, const cse::GradArgs& ga, const Group::Grad
   if (nr == 2 && size == 10) return cse::LaunchGradientSlot<2, 10>(ga, ch, form, s), true;
   if (nr == 3 && size == 3) return cse::LaunchGradientSlot<3, 3>(ga, ch, form, s), true;
   return false;
-}
-
-int DetectAffine(const cse_problem_desc* d, const cse_residual_group& g, const KindShape& k,
-                  Group* G) {
-  const int64_t n = g.num_blocks;
-  if (n == 0) return kTable;
-  // The affine kernels take one or two slots, at most three residuals; a
-  // user kind has them only for the shapes its header instantiates.
-  if (k.nb > 2 || k.nr > 3 || IsTestKind(g.functor_kind)) return kTable;
-  if (const cse_functor_ops* u = UserOps(g.functor_kind))
-    if (!UserAffine(u)) return kTable;
-  auto gidx = [&](int64_t i) {
-    return g.residual_block_index ? g.residual_block_index[i] : g.first_residual_block + i;
-  };
-  // Ambient sizes (state offsets) and tangent sizes (delta offsets, the
-  // Jacobian's columns).  Slot 0 of the quaternion camera may be on
-  // CSE_MANIFOLD_QUATERNION_EUCLIDEAN (then in every block): the kernel kind
-  // becomes kKindQuaternionTangent, which builds the plus-Jacobian itself.
-  const int ambient[2] = {k.s0, k.s1};
-  int sizes[2] = {k.s0, k.s1};
-  int manifold[2] = {CSE_MANIFOLD_MATRIX, CSE_MANIFOLD_MATRIX};
-  // The first block whose slot j is active (bases and the manifold come from it).
-  int64_t first[2] = {-1, -1};
-  for (int64_t i = 0; i < n && (first[0] < 0 || (k.nb > 1 && first[1] < 0)); ++i)
-    for (int j = 0; j < k.nb; ++j)
-      if (first[j] < 0 && !d->parameter_blocks[g.parameter_block_ids[i * k.nb + j]].is_constant)
-        first[j] = i;
-  for (int j = 0; j < k.nb; ++j)
-    if (first[j] < 0) return kTable;
-  if (g.functor_kind == CSE_FUNCTOR_SNAVELY_QUATERNION_2_10_3 &&
-      d->parameter_blocks[g.parameter_block_ids[first[0] * k.nb]].manifold ==
-          CSE_MANIFOLD_QUATERNION_EUCLIDEAN) {
-    manifold[0] = CSE_MANIFOLD_QUATERNION_EUCLIDEAN;
-    sizes[0] = k.s0 - 1;
-  }
-  G->slot0_manifold = manifold[0];
-  // Constant slot-0 blocks (a held camera) are allowed for the kinds with the
-  // constant-aware kernels (the 9-column cameras, cse::ShippedTuneC0).
-  const bool const0_ok = k.nb == 2 && (g.functor_kind == CSE_FUNCTOR_SNAVELY_2_9_3 ||
-                                       manifold[0] == CSE_MANIFOLD_QUATERNION_EUCLIDEAN);
-  // Parameters: active (slot 0 may be constant, above), no explicit
-  // plus-Jacobian, state/delta offsets affine in the id.
-  for (int j = 0; j < k.nb; ++j) {
-    const int32_t id0 = g.parameter_block_ids[first[j] * k.nb + j];
-    const cse_parameter_block& pb0 = d->parameter_blocks[id0];
-    G->state_base[j] = pb0.state_offset - (int64_t)ambient[j] * id0;
-    G->delta_base[j] = pb0.delta_offset - (int64_t)sizes[j] * id0;
-  }
-  // With constant slot-0 blocks the active ones need not be affine either
-  // (a held camera in the middle shifts the later ones' offsets): their values
-  // come through the repacked table, their gradient rows through a table.
-  G->const0 = false;
-  for (int64_t i = 0; i < n && !G->const0; ++i)
-    G->const0 = d->parameter_blocks[g.parameter_block_ids[i * k.nb]].is_constant != 0;
-  if (G->const0 && !const0_ok) return kTable;
-  for (int64_t i = 0; i < n; ++i)
-    for (int j = 0; j < k.nb; ++j) {
-      const int32_t id = g.parameter_block_ids[i * k.nb + j];
-      const cse_parameter_block& pb = d->parameter_blocks[id];
-      if (pb.is_constant) {
-        if (j != 0 || pb.size != ambient[0]) return kTable;
-        continue;
-      }
-      if (pb.plus_jacobian_offset >= 0 || pb.manifold != manifold[j] ||
-          pb.tangent_size != sizes[j] || pb.size != ambient[j])
-        return kTable;
-      if (j == 0 && G->const0) continue;
-      if (pb.state_offset != G->state_base[j] + (int64_t)ambient[j] * id) return kTable;
-      if (pb.delta_offset != G->delta_base[j] + (int64_t)sizes[j] * id) return kTable;
-    }
-  // Slot-0 id range (the repacked table of the cooperative gather).
-  int32_t lo = g.parameter_block_ids[0], hi = lo;
-  for (int64_t i = 0; i < n; ++i) {
-    lo = std::min(lo, g.parameter_block_ids[i * k.nb]);
-    hi = std::max(hi, g.parameter_block_ids[i * k.nb]);
-  }
-  G->slot0_lo = lo;
-  G->slot0_count = (int64_t)hi - lo + 1;
-  G->slot0_stride = (sizes[0] + 1) & ~1;  // per-block slot-0 gradient contributions
-  G->packed_stride = cse::PackedRowDoubles(ambient[0]);
-  // Residuals.
-  G->res_base = d->residual_layout[gidx(0)];
-  for (int64_t i = 0; i < n; ++i)
-    if (d->residual_layout[gidx(i)] != G->res_base + (int64_t)k.nr * i) return kTable;
-  // Jacobian rows.
-  if (!d->jacobian_per_residual_layout || !d->jacobian_per_residual_offsets) return kAffinePacked;
-  const int64_t* L = d->jacobian_per_residual_layout;
-  const int64_t* O = d->jacobian_per_residual_offsets;
-  if (G->const0) {
-    const int NR = k.nr, S0 = sizes[0], S1 = sizes[1];
-    auto act = [&](int64_t i) {
-      return !d->parameter_blocks[g.parameter_block_ids[i * k.nb]].is_constant;
-    };
-    const int64_t nchunks = (n + cse::kWave - 1) / cse::kWave;
-    // BlockSparseMatrix: the E (slot 1) cells affine, kR x S1 packed at
-    // e0 + kR*S1*i; the F cells of the blocks with an active camera packed in
-    // block order from f0 (a constant camera has none; its block's first
-    // active entries are the E rows).  Per chunk of 64 blocks: its first F
-    // cell, then the end of the F cells.
-    auto try_bsm = [&]() -> bool {
-      const int64_t f0 = O[L[gidx(first[0])]];
-      const int64_t e0 = O[L[gidx(0)] + (act(0) ? NR : 0)];
-      std::vector<int64_t> fb;
-      fb.reserve((size_t)nchunks + 1);
-      int64_t rank = 0;
-      for (int64_t i = 0; i < n; ++i) {
-        if (i % cse::kWave == 0) fb.push_back(f0 + (int64_t)NR * S0 * rank);
-        const int64_t base = L[gidx(i)];
-        int a = 0;
-        if (act(i)) {
-          for (int r = 0; r < NR; ++r)
-            if (O[base + r] != f0 + (int64_t)NR * S0 * rank + (int64_t)r * S0) return false;
-          ++rank;
-          a = 1;
-        }
-        for (int r = 0; r < NR; ++r)
-          if (O[base + a * NR + r] != e0 + (int64_t)NR * S1 * i + (int64_t)r * S1) return false;
-      }
-      for (int r = 0; r < NR; ++r) {
-        G->jac_base[0][r] = f0 + (int64_t)r * S0;
-        G->jac_base[1][r] = e0 + (int64_t)r * S1;
-      }
-      G->jac_stride[0] = (int64_t)NR * S0;
-      G->jac_stride[1] = (int64_t)NR * S1;
-      fb.push_back(f0 + (int64_t)NR * S0 * rank);
-      G->h_fbase = std::move(fb);
-      return true;
-    };
-    // CompressedRowSparseMatrix (compressed_row_jacobian_writer.cc:145-185):
-    // every block's rows packed in block order, NR x (S0 + S1) with an active
-    // camera (camera and point at fixed columns of the row) and NR x S1 with
-    // a held one (the point alone).  Per chunk: the offset of its first row,
-    // then the end.
-    auto try_crs = [&]() -> bool {
-      const int N = S0 + S1;
-      const int64_t b0 = L[gidx(first[0])];
-      const int64_t cam0 = O[b0], pt0 = O[b0 + NR];
-      const int64_t rb0 = std::min(cam0, pt0);
-      const int camcol = (int)(cam0 - rb0), ptcol = (int)(pt0 - rb0);
-      if (!((camcol == 0 && ptcol == S0) || (ptcol == 0 && camcol == S1))) return false;
-      const int64_t r0 = rb0 - (int64_t)NR * S1 * first[0];
-      std::vector<int64_t> cb;
-      cb.reserve((size_t)nchunks + 1);
-      int64_t pos = r0;
-      for (int64_t i = 0; i < n; ++i) {
-        if (i % cse::kWave == 0) cb.push_back(pos);
-        const int64_t base = L[gidx(i)];
-        if (act(i)) {
-          for (int r = 0; r < NR; ++r)
-            if (O[base + r] != pos + (int64_t)r * N + camcol ||
-                O[base + NR + r] != pos + (int64_t)r * N + ptcol)
-              return false;
-          pos += (int64_t)NR * N;
-        } else {
-          for (int r = 0; r < NR; ++r)
-            if (O[base + r] != pos + (int64_t)r * S1) return false;
-          pos += (int64_t)NR * S1;
-        }
-      }
-      cb.push_back(pos);
-      for (int r = 0; r < NR; ++r) {
-        G->jac_base[0][r] = r0 + (int64_t)r * N + camcol;
-        G->jac_base[1][r] = r0 + (int64_t)r * N + ptcol;
-      }
-      G->jac_stride[0] = G->jac_stride[1] = (int64_t)NR * N;
-      G->h_fbase = std::move(cb);
-      return true;
-    };
-    if (try_bsm()) return kAffinePacked;
-    if (try_crs()) return kAffineCrs;
-    return kTable;
-  }
-  for (int j = 0; j < k.nb; ++j)
-    for (int r = 0; r < k.nr; ++r) G->jac_base[j][r] = O[L[gidx(0)] + j * k.nr + r];
-  for (int j = 0; j < k.nb; ++j)
-    G->jac_stride[j] = n > 1 ? O[L[gidx(1)] + j * k.nr] - G->jac_base[j][0] : (int64_t)k.nr * sizes[j];
-  for (int64_t i = 0; i < n; ++i)
-    for (int j = 0; j < k.nb; ++j)
-      for (int r = 0; r < k.nr; ++r)
-        if (O[L[gidx(i)] + j * k.nr + r] != G->jac_base[j][r] + G->jac_stride[j] * i) return kTable;
-  const int N = sizes[0] + sizes[1];
-  // Shape 1: packed cells (BlockSparseMatrix).
-  bool packed = true;
-  for (int j = 0; j < k.nb; ++j) {
-    if (G->jac_stride[j] != (int64_t)k.nr * sizes[j]) packed = false;
-    for (int r = 0; r < k.nr; ++r)
-      if (G->jac_base[j][r] != G->jac_base[j][0] + (int64_t)r * sizes[j]) packed = false;
-  }
-  if (packed && !(G->jac_stride[0] == (int64_t)k.nr * N && k.nb > 1)) return kAffinePacked;
-  // Shape 2: interleaved rows (CompressedRowSparseMatrix): every slot has
-  // stride kR*N, row r of the block starts at row0 + r*N and each slot sits
-  // at a fixed column position inside the row, the slots tiling [0, N).
-  int64_t row0 = G->jac_base[0][0];
-  for (int j = 0; j < k.nb; ++j) row0 = std::min(row0, G->jac_base[j][0]);
-  bool cover[32] = {false};
-  for (int j = 0; j < k.nb; ++j) {
-    if (G->jac_stride[j] != (int64_t)k.nr * N) return kTable;
-    const int64_t col = G->jac_base[j][0] - row0;
-    if (col < 0 || col + sizes[j] > N) return kTable;
-    for (int c = 0; c < sizes[j]; ++c) {
-      if (cover[col + c]) return kTable;
-      cover[col + c] = true;
-    }
-    for (int r = 0; r < k.nr; ++r)
-      if (G->jac_base[j][r] != row0 + (int64_t)r * N + col) return kTable;
-  }
-  return kAffineCrs;
 }
 
 cse::GroupArgs MakeArgs(cse_evaluator* ev, Group& G, const double* state, double* res,
@@ -1064,119 +583,6 @@ cse::GroupArgs MakeArgs(cse_evaluator* ev, Group& G, const double* state, double
   a.plain0_state_base = G.plain0_state_base;
   a.plain0_delta_base = G.plain0_delta_base;
   return a;
-}
-
-// A table group whose slot-0 blocks are all plain: active, no manifold
-// (plus_jacobian_offset -1), tangent size = size = the kind's, state and
-// delta offsets affine in the id.  EvaluateTableKernel then forms their PbDev
-// records instead of loading them: one cache line less per lane for a
-// camera-like slot 0, whose lines the point stream evicts from L2 between
-// uses.
-void DetectPlain0(const cse_problem_desc* d, const cse_residual_group& g, Group* G) {
-  const KindShape& k = G->shape;
-  G->plain0 = false;
-  if (G->affine || G->n == 0) return;
-  const int S = k.sz[0];
-  const int32_t id0 = g.parameter_block_ids[0];
-  const int64_t sb = d->parameter_blocks[id0].state_offset - (int64_t)S * id0;
-  const int64_t db = d->parameter_blocks[id0].delta_offset - (int64_t)S * id0;
-  for (int64_t i = 0; i < G->n; ++i) {
-    const int32_t id = g.parameter_block_ids[i * k.nb];
-    const cse_parameter_block& p = d->parameter_blocks[id];
-    if (p.is_constant || p.manifold != CSE_MANIFOLD_MATRIX || p.plus_jacobian_offset != -1 ||
-        p.size != S || p.tangent_size != S || p.state_offset != sb + (int64_t)S * id ||
-        p.delta_offset != db + (int64_t)S * id)
-      return;
-  }
-  G->plain0 = true;
-  G->plain0_state_base = sb;
-  G->plain0_delta_base = db;
-}
-
-// The general kernel's store runs, found once per 64-block chunk (the
-// wave's blocks) by the tests TableStores makes on the device: flags
-// kTableRunFlagResiduals when the chunk's residuals are one run (NR apart),
-// kTableRunFlagBsm / Crs when every slot is active in all or none of its
-// blocks with one tangent size and its Jacobian rows form BlockSparseMatrix
-// cell runs / CompressedRow row blocks; then the residual run's start and
-// each active slot's first row.  [chunks][2 + nb]; shapes the kernel stages
-// (kTableStaged: NR x N <= 32) only.
-int BuildTableRuns(const cse_evaluator* ev, const cse_problem_desc* d, const cse_residual_group& g, Group* G,
-                   hipStream_t s) {
-  const KindShape& k = G->shape;
-  int N = 0;
-  for (int j = 0; j < k.nb; ++j) N += k.sz[j];
-  if (G->affine || G->n == 0 || k.nr * N > 32) return CSE_OK;
-  const int NB = k.nb, NR = k.nr, W = 2 + NB;
-  const int64_t n = G->n, nch = (n + cse::kWave - 1) / cse::kWave;
-  std::vector<int64_t> runs((size_t)(nch * W), 0);
-  auto gidx = [&](int64_t i) { return g.residual_block_index ? g.residual_block_index[i] : g.first_residual_block + i; };
-  auto pb = [&](int64_t i, int j) -> const cse_parameter_block& {
-    return d->parameter_blocks[g.parameter_block_ids[i * NB + j]];
-  };
-  for (int64_t c = 0; c < nch; ++c) {
-    const int64_t i0 = c * cse::kWave;
-    const int nb = (int)std::min<int64_t>(cse::kWave, n - i0);
-    int64_t* R = &runs[(size_t)(c * W)];
-    const int64_t off0 = d->residual_layout[gidx(i0)];
-    bool rr = true;
-    for (int l = 1; rr && l < nb; ++l) rr = d->residual_layout[gidx(i0 + l)] == off0 + (int64_t)NR * l;
-    if (rr) {
-      R[0] |= cse::kTableRunFlagResiduals;
-      R[1] = off0;
-    }
-    if (!ev->has_layout) continue;
-    bool cst[CSE_MAX_PARAMETER_BLOCKS];
-    int t[CSE_MAX_PARAMETER_BLOCKS];
-    bool uniform = true;
-    for (int j = 0; j < NB; ++j) {
-      cst[j] = pb(i0, j).is_constant != 0;
-      t[j] = pb(i0, j).tangent_size;
-      for (int l = 1; uniform && l < nb; ++l) {
-        const cse_parameter_block& p = pb(i0 + l, j);
-        uniform = (p.is_constant != 0) == cst[j] && (cst[j] || p.tangent_size == t[j]);
-      }
-    }
-    if (!uniform) continue;
-    // Row (j, kk) of lane l: offsets[layout[gidx] + a NR + kk], a = slot j's
-    // position among the active slots.
-    auto row = [&](int l, int a, int kk) {
-      return d->jacobian_per_residual_offsets[d->jacobian_per_residual_layout[gidx(i0 + l)] + (int64_t)a * NR + kk];
-    };
-    int64_t base[CSE_MAX_PARAMETER_BLOCKS] = {0};
-    int64_t r0 = INT64_MAX;
-    int w = 0, a = 0;
-    for (int j = 0; j < NB; ++j) {
-      if (cst[j]) continue;
-      base[j] = row(0, a++, 0);
-      r0 = std::min(r0, base[j]);
-      w += t[j];
-    }
-    bool bsm = true, crs = true;
-    a = 0;
-    for (int j = 0; j < NB; ++j) {
-      if (cst[j]) continue;
-      for (int l = 0; l < nb && (bsm || crs); ++l)
-        for (int kk = 0; kk < NR; ++kk) {
-          const int64_t v = row(l, a, kk);
-          bsm = bsm && v == base[j] + (int64_t)l * NR * t[j] + (int64_t)kk * t[j];
-          crs = crs && v == base[j] + (int64_t)l * NR * w + (int64_t)kk * w;
-        }
-      ++a;
-      const int64_t cj = base[j] - r0;
-      crs = crs && cj >= 0 && cj + t[j] <= w;
-      for (int j2 = 0; j2 < j; ++j2) {
-        if (cst[j2]) continue;
-        const int64_t c2 = base[j2] - r0;
-        crs = crs && (cj + t[j] <= c2 || c2 + t[j2] <= cj);
-      }
-    }
-    R[0] |= (bsm ? cse::kTableRunFlagBsm : 0) | (crs ? cse::kTableRunFlagCrs : 0);
-    for (int j = 0; j < NB; ++j) R[2 + j] = base[j];
-  }
-  int rc = G->runs.upload(runs.data(), runs.size(), s);
-  if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = Fail(CSE_ERR_HIP, "table runs upload failed");
-  return rc;
 }
 
 int FoldTiming(cse_evaluator* ev) {
@@ -1286,19 +692,10 @@ int LaunchCameraGradKernel(cse_evaluator* ev, Group& G, const double* state, hip
   if (P.nchunks > 0) {
     auto launch = [&](auto kd) {
       using K = decltype(kd);
-      switch (G.loss.kind) {
-        case CSE_LOSS_HUBER:
-          hipLaunchKernelGGL((cse::CameraGradientKernel<K, cse::kLossHuber, W>), grid,
-                             dim3(W * cse::kWave), 0, s, cg);
-          break;
-        case CSE_LOSS_CAUCHY:
-          hipLaunchKernelGGL((cse::CameraGradientKernel<K, cse::kLossCauchy, W>), grid,
-                             dim3(W * cse::kWave), 0, s, cg);
-          break;
-        default:
-          hipLaunchKernelGGL((cse::CameraGradientKernel<K, cse::kLossTrivial, W>), grid,
-                             dim3(W * cse::kWave), 0, s, cg);
-      }
+      VisitLoss(G.loss.kind, [&](auto l) {
+        hipLaunchKernelGGL((cse::CameraGradientKernel<K, decltype(l)::value, W>), grid,
+                           dim3(W * cse::kWave), 0, s, cg);
+      });
     };
     if (G.jet) cse::LaunchJetCameraGradient(G.loss.kind, cg, cg.nslots, s);
     else if (G.kind == kKindQuaternionTangent) launch(cse::SnavelyQuaternionTangentKind{});
@@ -1340,70 +737,42 @@ int LaunchCameraGradReduce(Group& G, double* out, hipStream_t s, bool assign = f
   return CSE_OK;
 }
 
-// The implicit Schur complement's structure (cse_schur_*): one Snavely
-// group on the fused-gradient path with the BlockSparseMatrix layout, its
-// e blocks (slot 1, points) the leading columns [0, e_cols) and its f blocks
-// (slot 0, cameras) the rest, as ITERATIVE_SCHUR's elimination ordering puts
-// them (iterative_schur_complement_solver.cc:66-80).  The e-block runs are cut
-// into wave chunks of whole runs; longer runs are listed as big.
-int BuildSchurPlan(cse_evaluator* ev, const cse_problem_desc* d, hipStream_t s) {
-  auto& S = ev->schur;
-  S.eligible = false;
-  if (ev->groups.size() != 1 || d->num_groups != 1) return CSE_OK;
-  const Group& G = ev->groups[0];
-  if (!G.fuse_ok || G.policy != kAffinePacked || !SnavelyShaped(G) ||
-      !ev->has_layout || ev->num_constant > 0)
-    return CSE_OK;
-  const cse_residual_group& g = d->groups[0];
-  const int32_t* ids = g.parameter_block_ids;
-  const int64_t n = g.num_blocks;
-  int32_t pmin = ids[1], pmax = ids[1], cmin = ids[0], cmax = ids[0];
-  for (int64_t i = 0; i < n; ++i) {
-    pmin = std::min(pmin, ids[2 * i + 1]);
-    pmax = std::max(pmax, ids[2 * i + 1]);
-    cmin = std::min(cmin, ids[2 * i]);
-    cmax = std::max(cmax, ids[2 * i]);
-  }
-  const int64_t e_lo = G.delta_base[1] + 3LL * pmin, e_hi = G.delta_base[1] + 3LL * pmax + 3;
-  const int64_t f_lo = G.delta_base[0] + 9LL * cmin, f_hi = G.delta_base[0] + 9LL * cmax + 9;
-  if (e_lo < 0 || f_lo != e_hi || f_hi != ev->num_effective || e_lo != 0) return CSE_OK;
-  S.e_cols = e_hi;
-  S.f_cols = f_hi - f_lo;
-  S.f_col_base = G.delta_base[0] - S.e_cols;
-  // One pass over the runs of equal e block: small runs are packed into
-  // chunks of at most a wave ([begin, end) pairs; chunks never straddle a
-  // big run), big runs listed on their own.
-  std::vector<int64_t> ranges, big;
-  std::vector<int32_t> cams;
-  bool dup = false;
-  int64_t run_start = 0, chunk_lo = 0;
-  for (int64_t i = 1; i <= n; ++i) {
-    if (i < n && ids[2 * i + 1] == ids[2 * (i - 1) + 1]) continue;
-    const int64_t len = i - run_start;  // the run [run_start, i)
-    cams.assign(len, 0);
-    for (int64_t k = 0; k < len; ++k) cams[k] = ids[2 * (run_start + k)];
-    std::sort(cams.begin(), cams.end());
-    dup = dup || std::adjacent_find(cams.begin(), cams.end()) != cams.end();
-    if (len > cse::kWave) {
-      if (run_start > chunk_lo) ranges.insert(ranges.end(), {chunk_lo, run_start});
-      big.insert(big.end(), {run_start, i});
-      chunk_lo = i;
-    } else if (i - chunk_lo > cse::kWave) {
-      ranges.insert(ranges.end(), {chunk_lo, run_start});
-      chunk_lo = run_start;
-    }
-    run_start = i;
-  }
-  if (n > chunk_lo) ranges.insert(ranges.end(), {chunk_lo, n});
-  std::vector<int64_t>& begins = ranges;
-  S.duplicates = dup;
-  S.nchunks = (int64_t)begins.size() / 2;
-  S.nbig = (int64_t)big.size() / 2;
+// One planned group's tables to the device (cse::PlanGroup made T), its ids
+// and functor data, and the buffers the plan sizes.  Returns once every copy
+// has completed, so the caller may release T.
+int UploadGroup(const cse_residual_group& g, const cse::GroupTables& T, Group* Gp, hipStream_t s) {
+  Group& G = *Gp;
+  const KindShape& k = G.shape;
   int rc;
-  if ((rc = S.chunk_begin.upload(begins.data(), begins.size(), s))) return rc;
-  if ((rc = S.big.upload(big.data(), big.size(), s))) return rc;
-  if (hipStreamSynchronize(s) != hipSuccess) return Fail(CSE_ERR_HIP, "Schur plan upload failed");
-  S.eligible = true;
+  if (G.repack0 && (rc = G.packed0.alloc((size_t)G.slot0_count * G.packed_stride))) return rc;
+  if ((rc = G.act0.upload(T.bits.data(), T.bits.size(), s))) return rc;
+  if ((rc = G.src0.upload(T.src.data(), T.src.size(), s))) return rc;
+  if ((rc = G.delta0.upload(T.dlt.data(), T.dlt.size(), s))) return rc;
+  if ((rc = G.fbase.upload(T.fbase.data(), T.fbase.size(), s))) return rc;
+  if ((rc = G.prev_seg.upload(T.prev_seg.data(), T.prev_seg.size(), s))) return rc;
+  if ((rc = G.side.alloc(T.prev_seg.size() * 16))) return rc;
+  for (int j = 0; j < 2; ++j) {
+    Group::GradPlan& D = G.grad[j];
+    const cse::GradTables& H = T.grad[j];
+    static_cast<cse::GradPlanInfo&>(D) = T.grad_info[j];
+    if ((rc = D.perm.upload(H.perm.data(), H.perm.size(), s))) return rc;
+    if ((rc = D.off.upload(H.off.data(), H.off.size(), s))) return rc;
+    if ((rc = D.chunk_order.upload(H.chunk_order.data(), H.chunk_order.size(), s))) return rc;
+    if ((rc = D.chunk_begin.upload(H.chunk_begin.data(), H.chunk_begin.size(), s))) return rc;
+    if ((rc = D.chunk_off.upload(H.chunk_off.data(), H.chunk_off.size(), s))) return rc;
+    if ((rc = D.chunk_pb.upload(H.chunk_pb.data(), H.chunk_pb.size(), s))) return rc;
+    const int size = j == 0 ? k.s0 : k.s1;
+    if (D.ready && !D.sorted &&
+        (rc = D.chunk_partial.alloc((size_t)std::max<int64_t>(1, D.nchunks) * size)))
+      return rc;
+  }
+  if ((rc = G.runs.upload(T.runs.data(), T.runs.size(), s))) return rc;
+  if ((rc = G.ids.upload(g.parameter_block_ids, (size_t)g.num_blocks * k.nb, s))) return rc;
+  if ((rc = G.data.upload(g.functor_data, (size_t)g.num_blocks * k.data, s))) return rc;
+  if ((!G.affine || G.const0) && g.residual_block_index &&
+      (rc = G.gindex.upload(g.residual_block_index, (size_t)g.num_blocks, s)))
+    return rc;
+  if (hipStreamSynchronize(s) != hipSuccess) return Fail(CSE_ERR_HIP, "upload failed");
   return CSE_OK;
 }
 
@@ -1416,21 +785,24 @@ int BuildSchurPlan(cse_evaluator* ev, const cse_problem_desc* d, hipStream_t s) 
 struct GradPath {
   bool grad_pass = false, fused = false, recompute = false;
 };
+// Does gradient_mode give a fused-eligible group the fused form?
+// Mode 1 (post-pass) has no form over the packed F cells of a group with
+// constant slot-0 blocks: it takes mode 0's fused form (also fixed order).
+// The Jet form has no mode-3 kernel (contributions in block order): the
+// post-pass instead, as for groups without a fused form.
+bool FusedGradMode(const cse_evaluator* ev, const Group& G) {
+  const int mode = ev->opts.gradient_mode;
+  return G.fuse_ok && (mode == 0 || (!G.user && ((mode == 3 && !G.jet) || (mode == 1 && G.const0))));
+}
 GradPath GradPathOf(const cse_evaluator* ev, const Group& G, bool grad, bool res, bool jac) {
   GradPath p;
   p.grad_pass = grad && res && jac && G.affine && ev->opts.gradient_mode != 2;
   for (int j = 0; j < G.shape.nb; ++j) p.grad_pass = p.grad_pass && G.grad[j].ready;
-  const int mode = ev->opts.gradient_mode;
-  // Mode 1 (post-pass) has no form over the packed F cells of a group with
-  // constant slot-0 blocks: it takes mode 0's fused form (also fixed order).
-  // The Jet form has no mode-3 kernel (contributions in block order): the
-  // post-pass instead, as for groups without a fused form.
-  p.fused = p.grad_pass && G.fuse_ok &&
-            (mode == 0 || (!G.user && ((mode == 3 && !G.jet) || (mode == 1 && G.const0))));
+  p.fused = p.grad_pass && FusedGradMode(ev, G);
   // Constant slot-0 blocks: no post-pass over the packed F cells (in-kernel
   // atomics instead, active cameras only).
   if (G.const0 && !p.fused) p.grad_pass = false;
-  p.recompute = p.fused && mode != 3;
+  p.recompute = p.fused && ev->opts.gradient_mode != 3;
   return p;
 }
 
@@ -1530,7 +902,7 @@ int Enqueue(cse_evaluator* ev, const double* d_state, double* d_cost, double* d_
       // The 64-byte sectors two held-camera chunks share (the full chunks
       // stored their heads and tails in side slots), when the full chunks
       // took that tail: the same base alignment test as the kernel.
-      if (cse::HeldWindowsAligned(d_res, G.res_base, d_jac, G.jac_base[1][0], G.h_fbase[0])) {
+      if (cse::HeldWindowsAligned(d_res, G.res_base, d_jac, G.jac_base[1][0], G.fbase0)) {
         const int64_t nchunks = (G.n + cse::kWave - 1) / cse::kWave;
         const int64_t threads = 4 * nchunks;
         hipLaunchKernelGGL(cse::HeldSectorFixupKernel,
@@ -1619,7 +991,10 @@ const char* cse_build_info(void) {
 int cse_create(const cse_problem_desc* d, const cse_options* options, cse_evaluator** out) {
   if (!out) return Fail(CSE_ERR_INVALID, "null out");
   *out = nullptr;
-  int rc = Validate(d);
+  // Validation comes in two parts, so that every refusal keeps its place in
+  // the order callers know: the descriptor's own fields before the options,
+  // the groups and their blocks (ValidateGroups) after the device is picked.
+  int rc = cse::Validate(d);
   if (rc) return rc;
   cse_evaluator* ev = new (std::nothrow) cse_evaluator();
   if (!ev) return Fail(CSE_ERR_OOM, "host allocation failed");
@@ -1660,289 +1035,41 @@ int cse_create(const cse_problem_desc* d, const cse_options* options, cse_evalua
   ev->num_residuals = d->num_residuals;
   ev->num_jacobian_values = d->num_jacobian_values;
   ev->num_plus_jacobian_values = d->num_plus_jacobian_values;
-  ev->has_layout = d->jacobian_per_residual_layout && d->jacobian_per_residual_offsets;
-  {
-    // Plus runs: active blocks sorted by state offset, merged while
-    // contiguous with a constant delta shift.
-    std::vector<std::pair<int64_t, int64_t>> blocks;  // (state_offset, index)
-    for (int64_t b = 0; b < d->num_parameter_blocks; ++b) {
-      const cse_parameter_block& pb = d->parameter_blocks[b];
-      if (pb.is_constant) continue;
-      if (pb.manifold == CSE_MANIFOLD_QUATERNION_EUCLIDEAN) {
-        ev->plus_quat_host.push_back({pb.state_offset, pb.delta_offset, pb.size, 0});
-        continue;
-      }
-      if (pb.plus_jacobian_offset >= 0 || pb.tangent_size != pb.size) ev->plus_supported = false;
-      blocks.emplace_back(pb.state_offset, b);
-    }
-    std::sort(blocks.begin(), blocks.end());
-    for (const auto& e : blocks) {
-      const cse_parameter_block& pb = d->parameter_blocks[e.second];
-      const int64_t shift = pb.state_offset - pb.delta_offset;
-      auto& R = ev->plus_runs_host;
-      if (!R.empty() && R.back().state_begin + R.back().length == pb.state_offset &&
-          R.back().delta_shift == shift)
-        R.back().length += pb.size;
-      else
-        R.push_back({pb.state_offset, pb.size, shift});
-    }
-  }
 
-  // Groups.
-  int64_t covered_res = 0, covered_jac = 0;
-  std::vector<char> seen(d->num_parameter_blocks, 0);
-  // Which (group, slot) uses each parameter block: -1 none, -2 several.
-  std::vector<int32_t> owner(d->num_parameter_blocks, -1);
+  // Validate, then plan and upload one group at a time: a group's host
+  // tables (UploadGroup waits for their copies) die before the next is planned.
+  cse::ProgramPlan P;
+  if ((rc = cse::ValidateGroups(d, &CseUserKind, &P))) return bail(rc);
+  ev->has_layout = P.has_layout;
+  ev->groups.resize((size_t)d->num_groups);
   for (int gi = 0; gi < d->num_groups; ++gi) {
-    const cse_residual_group& g = d->groups[gi];
-    Group G;
-    if (g.functor_kind < 0 || !ShapeOf(g.functor_kind, &G.shape))
-      return bail(Fail(CSE_ERR_UNSUPPORTED, "unknown functor kind " + std::to_string(g.functor_kind)));
-    if (g.loss.kind < CSE_LOSS_TRIVIAL || g.loss.kind > CSE_LOSS_USER)
-      return bail(Fail(CSE_ERR_UNSUPPORTED, "unknown loss kind " + std::to_string(g.loss.kind)));
-    if (IsTestKind(g.functor_kind) && (g.loss.kind != CSE_LOSS_TRIVIAL || g.loss.scaled))
-      return bail(Fail(CSE_ERR_UNSUPPORTED, "test functor kinds take the trivial loss only"));
-    G.user = UserOps(g.functor_kind);
-    if (G.user) {
-      // The kernels of a user kind apply the loss they were built with
-      // (AutoDiffResidualBlockCUDAEvaluator<F, LossFunctionCUDA, ...>).
-      {
-        std::lock_guard<std::mutex> lock(g_user_mu);
-        G.user_name = g_user_kinds[(size_t)(g.functor_kind - CSE_FUNCTOR_USER_FIRST)]->name;
-      }
-      if (g.loss.kind != G.user->loss_kind)
-        return bail(Fail(CSE_ERR_INVALID, "group " + std::to_string(gi) + ": user functor kind " +
-                                              G.user_name + " was registered with loss kind " +
-                                              std::to_string(G.user->loss_kind) + ", the group has " +
-                                              std::to_string(g.loss.kind)));
-    } else if (g.loss.kind == CSE_LOSS_USER) {
-      return bail(Fail(CSE_ERR_INVALID, "the user loss kind (3) needs a user functor kind registered with it"));
-    }
-    if (g.num_blocks < 0 || (g.num_blocks > 0 && (!g.parameter_block_ids || !g.functor_data)))
-      return bail(Fail(CSE_ERR_INVALID, "group " + std::to_string(gi) + " arrays missing"));
-    G.kind = g.functor_kind;
-    G.loss = g.loss;
-    G.n = g.num_blocks;
-    G.first = g.first_residual_block;
-    const KindShape& k = G.shape;
-    for (int64_t i = 0; i < g.num_blocks; ++i) {
-      const int64_t gidx = g.residual_block_index ? g.residual_block_index[i] : g.first_residual_block + i;
-      if (gidx < 0 || gidx >= d->num_residual_blocks)
-        return bail(Fail(CSE_ERR_INVALID, "residual block index out of range in group " + std::to_string(gi)));
-      if (d->residual_layout[gidx] < 0 || d->residual_layout[gidx] + k.nr > d->num_residuals)
-        return bail(Fail(CSE_ERR_INVALID, "residual_layout out of range"));
-      covered_res += k.nr;
-      for (int j = 0; j < k.nb; ++j) {
-        const int32_t id = g.parameter_block_ids[i * k.nb + j];
-        if (id < 0 || id >= d->num_parameter_blocks)
-          return bail(Fail(CSE_ERR_INVALID, "parameter block id out of range in group " + std::to_string(gi)));
-        const int want = k.sz[j];
-        const cse_parameter_block& pb = d->parameter_blocks[id];
-        if (pb.size != want)
-          return bail(Fail(CSE_ERR_INVALID, "parameter block size does not match the functor"));
-        if (!pb.is_constant) covered_jac += (int64_t)k.nr * pb.tangent_size;
-        const int32_t tag = 2 * gi + j;
-        if (owner[id] == -1) owner[id] = tag;
-        else if (owner[id] != tag) owner[id] = -2;
-        if (!seen[id]) {
-          seen[id] = 1;
-          ev->bytes_jac += 8LL * pb.size;
-          ev->bytes_res += 8LL * pb.size;
-        }
-      }
-      if (ev->has_layout) {
-        const int64_t base = d->jacobian_per_residual_layout[gidx];
-        int na = 0;
-        for (int j = 0; j < k.nb; ++j)
-          if (!d->parameter_blocks[g.parameter_block_ids[i * k.nb + j]].is_constant) ++na;
-        if (base < 0 || base + (int64_t)na * k.nr > d->num_jacobian_per_residual_offsets)
-          return bail(Fail(CSE_ERR_INVALID, "jacobian_per_residual_layout out of range"));
-        int a = 0;
-        for (int j = 0; j < k.nb; ++j) {
-          const cse_parameter_block& pb = d->parameter_blocks[g.parameter_block_ids[i * k.nb + j]];
-          if (pb.is_constant) continue;
-          for (int r = 0; r < k.nr; ++r) {
-            const int64_t off = d->jacobian_per_residual_offsets[base + a * k.nr + r];
-            if (off < 0 || off + pb.tangent_size > d->num_jacobian_values)
-              return bail(Fail(CSE_ERR_INVALID, "jacobian offset out of range"));
-          }
-          ++a;
-        }
-      }
-    }
-    const int64_t per_block = 8LL * k.data + 4LL * k.nb + 8LL * k.nr;
-    ev->bytes_res += per_block * g.num_blocks;
-    ev->bytes_jac += per_block * g.num_blocks;
-    G.policy = ev->opts.force_general_layout ? kTable : DetectAffine(d, g, k, &G);
-    G.affine = G.policy != kTable;
-    if (!G.affine) G.const0 = false;  // DetectAffine may have set it before giving up
-    if (G.affine && g.functor_kind == CSE_FUNCTOR_SNAVELY_QUATERNION_2_10_3 &&
-        G.slot0_manifold == CSE_MANIFOLD_QUATERNION_EUCLIDEAN) {
-      // Slot 0 on the quaternion manifold (DetectAffine checked every active
-      // block; a held camera's own manifold is irrelevant): the kernel kind
-      // with the tangent Jacobian (k follows G.shape).
-      G.kind = kKindQuaternionTangent;
-      ShapeOf(G.kind, &G.shape);
-    }
-    // Constant slot-0 blocks need the repacked table (their values come from
-    // the constant state through it).
-    if (G.const0 && G.slot0_count > (1 << 20)) {
-      G.policy = kTable;
-      G.affine = false;
-      G.const0 = false;
-      if (G.kind == kKindQuaternionTangent) {
-        G.kind = g.functor_kind;
-        ShapeOf(G.kind, &G.shape);
-      }
-    }
-    // The Jet form of the Snavely functor (cse_options.jacobian_form) is
-    // instantiated for the affine kernels with the LDS-DMA gather and without
-    // held cameras, and for the table kernel: other Snavely groups take the
-    // table path.
-    G.jet = ev->opts.jacobian_form == CSE_JACOBIAN_JET && g.functor_kind == CSE_FUNCTOR_SNAVELY_2_9_3;
-    if (G.jet && G.affine && (G.const0 || G.slot0_count <= 0 || G.slot0_count > (1 << 20))) {
-      G.policy = kTable;
-      G.affine = false;
-      G.const0 = false;
-    }
-    // Table-path tables: also for const0 groups (their J products use the
-    // table kernels).
-    if (G.const0) ev->any_general = true;
-    if (!G.affine) ev->any_general = true;
-    if (G.affine) {
-      const int64_t chunks = (g.num_blocks + cse::kWave - 1) / cse::kWave;
-      G.num_wg = std::max<int64_t>(1, (chunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock);
-    } else {
-      G.num_wg = (g.num_blocks + cse::kBlockThreads - 1) / cse::kBlockThreads;
-    }
-    // Every kernel writes one cost partial per wave.
-    G.partial_offset = ev->total_wg;
-    ev->total_wg += G.num_wg * cse::kWavesPerBlock;
-    // The LDS-DMA gather reads slot 0 from a repacked copy refreshed every
-    // evaluation; worth it while the slot-0 id range is small (BAL: the
-    // cameras), otherwise gather 8-byte pieces from the state directly.
-    if (G.affine && G.slot0_count > 0 && G.slot0_count <= (1 << 20) &&
-        (rc = G.packed0.alloc((size_t)G.slot0_count * G.packed_stride)))
-      return bail(rc);
-    if (G.const0) {
-      std::vector<uint32_t> bits((size_t)((G.slot0_count + 31) / 32), 0u);
-      std::vector<int64_t> src((size_t)G.slot0_count, 0), dlt((size_t)G.slot0_count, -1);
-      // Ids in the range that are not camera-sized rows in bounds (blocks no
-      // block of the group uses) repack the first active camera (never read).
-      const int64_t fallback = G.state_base[0] + (int64_t)k.x0 * G.slot0_lo;  // overwritten below
-      int64_t first_active = -1;
-      for (int64_t q = 0; q < G.slot0_count && first_active < 0; ++q) {
-        const cse_parameter_block& pb = d->parameter_blocks[G.slot0_lo + q];
-        if (!pb.is_constant && pb.size == k.x0) first_active = pb.state_offset;
-      }
-      for (int64_t q = 0; q < G.slot0_count; ++q) {
-        const cse_parameter_block& pb = d->parameter_blocks[G.slot0_lo + q];
-        const bool fits = pb.size == k.x0 && pb.state_offset >= 0 &&
-                          pb.state_offset + k.x0 <= (pb.is_constant ? d->num_constant_parameters
-                                                                    : d->num_parameters);
-        if (!fits) {
-          src[q] = first_active >= 0 ? first_active : fallback;
-        } else if (pb.is_constant) {
-          src[q] = -1 - pb.state_offset;
-        } else {
-          bits[q >> 5] |= 1u << (q & 31);
-          src[q] = pb.state_offset;
-          dlt[q] = pb.delta_offset;
-        }
-      }
-      if ((rc = G.act0.upload(bits.data(), bits.size(), s))) return bail(rc);
-      if ((rc = G.src0.upload(src.data(), src.size(), s))) return bail(rc);
-      if ((rc = G.delta0.upload(dlt.data(), dlt.size(), s))) return bail(rc);
-      if (!G.h_fbase.empty() && (rc = G.fbase.upload(G.h_fbase.data(), G.h_fbase.size(), s)))
-        return bail(rc);
-      if (!G.h_fbase.empty()) {
-        const int64_t nchunks = (int64_t)G.h_fbase.size() - 1;
-        std::vector<int32_t> prev((size_t)nchunks, -1);
-        int32_t last = -1;
-        for (int64_t c = 0; c < nchunks; ++c) {
-          prev[c] = last;
-          if (G.h_fbase[c + 1] > G.h_fbase[c]) last = (int32_t)c;
-        }
-        if ((rc = G.prev_seg.upload(prev.data(), prev.size(), s))) return bail(rc);
-        if ((rc = G.side.alloc((size_t)nchunks * 16))) return bail(rc);
-      }
-      if (hipStreamSynchronize(s) != hipSuccess) return bail(Fail(CSE_ERR_HIP, "upload failed"));
-    }
-    if (G.affine && ev->has_layout) {
-      const int sizes[2] = {k.s0, k.s1};
-      for (int j = 0; j < k.nb; ++j)
-        if (GradSupported(k.nr, sizes[j], G.user, j) &&
-            (rc = BuildGradPlan(g, k, j, &G.grad[j], s,
-                                j == 0 && G.const0 ? d->parameter_blocks : nullptr,
-                                j == 0 && k.nb == 2 && (FusedKind(G.kind) || UserFused(G))
-                                    ? CamGradPasses(g, k)
-                                    : 1)))
-          return bail(rc);
-    }
-    if ((rc = BuildTableRuns(ev, d, g, &G, s))) return bail(rc);
-    DetectPlain0(d, g, &G);
-    if (G.plain0) {
-      // A plain slot 0 of a small id range (the cameras) is read from a
-      // repacked copy, as the affine kernels read it (RepackSlot0Kernel, every
-      // evaluation): one 128-byte row a lane instead of its values at an
-      // 8-byte alignment.
-      int32_t lo = INT32_MAX, hi = INT32_MIN;
-      for (int64_t i = 0; i < g.num_blocks; ++i) {
-        lo = std::min(lo, g.parameter_block_ids[i * k.nb]);
-        hi = std::max(hi, g.parameter_block_ids[i * k.nb]);
-      }
-      const int64_t count = (int64_t)hi - lo + 1;
-      if (k.sz[0] <= 16 && count <= (1 << 20)) {
-        G.slot0_lo = lo;
-        G.slot0_count = count;
-        G.packed_stride = cse::PackedRowDoubles(k.sz[0]);
-        G.state_base[0] = G.plain0_state_base;
-        if ((rc = G.packed0.alloc((size_t)count * G.packed_stride))) return bail(rc);
-      }
-    }
-    if ((rc = G.ids.upload(g.parameter_block_ids, (size_t)g.num_blocks * k.nb, s))) return bail(rc);
-    if ((rc = G.data.upload(g.functor_data, (size_t)g.num_blocks * k.data, s))) return bail(rc);
-    if ((!G.affine || G.const0) && g.residual_block_index &&
-        (rc = G.gindex.upload(g.residual_block_index, (size_t)g.num_blocks, s)))
-      return bail(rc);
-    ev->groups.push_back(std::move(G));
-  }
-  ev->bytes_jac += 8LL * covered_jac;
-  // Fused gradient eligibility: a Snavely group on the affine LDS-DMA path
-  // whose slot-1 blocks are sorted (identity plan) and used by no other
-  // group or slot (the fused kernel stores their rows, it does not add),
-  // and whose slot-0 blocks have a chunked plan.
-  for (int gi = 0; gi < (int)ev->groups.size(); ++gi) {
     Group& G = ev->groups[gi];
-    bool ok = (FusedKind(G.kind) || UserFused(G)) && G.affine && G.n > 0 && G.packed0.p &&
-              G.grad[0].ready && G.grad[0].perm.p && G.grad[0].nchunks > 0 && G.grad[1].ready &&
-              G.grad[1].perm.p == nullptr;
     const cse_residual_group& g = d->groups[gi];
-    for (int64_t i = 0; ok && i < g.num_blocks; ++i)
-      ok = owner[g.parameter_block_ids[2 * i + 1]] == 2 * gi + 1;
-    G.fuse_ok = ok;
-    G.grad_exact = ok && ev->groups.size() == 1 && d->num_groups == 1 && !G.const0 &&
-                   ev->num_constant == 0 && G.shape.s1 == 3 && G.grad[0].all_present &&
-                   G.grad[1].all_present &&
-                   G.shape.s0 * G.grad[0].count + 3 * G.grad[1].count == ev->num_effective;
+    cse::GroupTables T;
+    cse::PlanGroup(d, ev->opts, gi, &P, &G, &T);
+    G.user_name = P.user_names[gi];
+    if ((rc = UploadGroup(g, T, &G, s))) return bail(rc);
   }
-  if ((rc = BuildSchurPlan(ev, d, s))) return bail(rc);
-  ev->res_covered = covered_res == d->num_residuals;
-  ev->jac_covered = covered_jac == d->num_jacobian_values;
+  cse::PlanProgram(d, d->num_groups == 1 ? &ev->groups[0] : nullptr, &P);
+  ev->res_covered = P.res_covered;
+  ev->jac_covered = P.jac_covered;
+  ev->bytes_res = P.bytes_res;
+  ev->bytes_jac = P.bytes_jac;
+  ev->total_wg = P.total_wg;
+  ev->any_general = P.any_general;
+  ev->plus_supported = P.plus_supported;
+  ev->plus_runs_host = std::move(P.plus_runs);
+  ev->plus_quat_host = std::move(P.plus_quat);
+  static_cast<cse::SchurPlan&>(ev->schur) = P.schur;
 
   // Program-level device state.
+  if ((rc = ev->schur.chunk_begin.upload(P.schur_chunk_begin.data(), P.schur_chunk_begin.size(), s)))
+    return bail(rc);
+  if ((rc = ev->schur.big.upload(P.schur_big.data(), P.schur_big.size(), s))) return bail(rc);
   if ((rc = ev->cstate.upload(d->constant_state, (size_t)d->num_constant_parameters, s))) return bail(rc);
   if ((rc = ev->plus_jac.upload(d->plus_jacobians, (size_t)d->num_plus_jacobian_values, s))) return bail(rc);
   if (ev->any_general) {
-    std::vector<cse::PbDev> pbs(d->num_parameter_blocks);
-    for (int64_t b = 0; b < d->num_parameter_blocks; ++b) {
-      const cse_parameter_block& pb = d->parameter_blocks[b];
-      const int64_t pj = pb.manifold == CSE_MANIFOLD_QUATERNION_EUCLIDEAN
-                             ? cse::kPlusJacobianQuaternion
-                             : pb.plus_jacobian_offset;
-      pbs[b] = {pb.state_offset, pb.delta_offset, pj, pb.tangent_size, pb.is_constant};
-    }
-    if ((rc = ev->pbs.upload(pbs.data(), pbs.size(), s))) return bail(rc);
+    if ((rc = ev->pbs.upload(P.pbs.data(), P.pbs.size(), s))) return bail(rc);
     if ((rc = ev->res_layout.upload(d->residual_layout, (size_t)d->num_residual_blocks, s))) return bail(rc);
     if (ev->has_layout) {
       if ((rc = ev->jac_layout.upload(d->jacobian_per_residual_layout, (size_t)d->num_residual_blocks, s)))
@@ -1963,6 +1090,7 @@ int cse_create(const cse_problem_desc* d, const cse_options* options, cse_evalua
     return bail(Fail(CSE_ERR_HIP, "memset failed"));
   if (hipHostMalloc(&ev->status_host, sizeof(int)) != hipSuccess)
     return bail(Fail(CSE_ERR_HIP, "hipHostMalloc failed"));
+  // The copies read P's tables: wait before P goes out of scope.
   if (hipStreamSynchronize(s) != hipSuccess) return bail(Fail(CSE_ERR_HIP, "upload failed"));
   *out = ev;
   return CSE_OK;
@@ -2511,7 +1639,7 @@ int cse_create_multi(const cse_problem_desc* d, const cse_options* options, cons
                      int32_t num_devices, cse_evaluator** out) {
   if (!out) return Fail(CSE_ERR_INVALID, "null out");
   *out = nullptr;
-  int rc = Validate(d);
+  int rc = cse::Validate(d);
   if (rc) return rc;
   if (options && (options->gradient_mode < 0 || options->gradient_mode > 3))
     return Fail(CSE_ERR_INVALID, "gradient_mode " + std::to_string(options->gradient_mode) +
@@ -2591,7 +1719,7 @@ int cse_register_functor(const cse_functor_ops* ops, int32_t* kind) {
   for (int c = 0; c < 2; ++c)
     for (int j = 0; j < 2; ++j)
       for (int d = 0; d < 2; ++d) any_affine = any_affine || ops->affine[c][j][d];
-  if (any_affine && (!UserAffine(ops) || nb > 2 || ops->num_residuals > 3))
+  if (any_affine && (!cse::UserAffine(ops) || nb > 2 || ops->num_residuals > 3))
     return Fail(CSE_ERR_INVALID, "functor " + name + ": affine kernels must come as all eight, "
                                                      "for at most two blocks and three residuals");
   if (fused && (!any_affine || nb != 2 || ops->parameter_block_sizes[1] != 3 ||
@@ -2640,12 +1768,7 @@ int cse_get_info(cse_evaluator* ev, cse_info* info) {
   info->num_groups = (int32_t)ev->groups.size();
   for (auto& G : ev->groups) {
     info->num_affine_groups += G.affine ? 1 : 0;
-    info->num_fused_gradient_groups +=
-        (G.fuse_ok && (ev->opts.gradient_mode == 0 ||
-                       (!G.user && ((ev->opts.gradient_mode == 3 && !G.jet) ||
-                                    (ev->opts.gradient_mode == 1 && G.const0)))))
-            ? 1
-            : 0;
+    info->num_fused_gradient_groups += FusedGradMode(ev, G) ? 1 : 0;
   }
   info->device = ev->device;
   info->bytes_jacobian_eval = ev->bytes_jac;

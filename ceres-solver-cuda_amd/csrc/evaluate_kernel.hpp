@@ -1479,7 +1479,6 @@ __global__ __launch_bounds__(kBlockThreads) void SortSlot0InputsAnyKernel(const 
 // residuals 48 of the kernel's table bytes a block, profiles/round6/r6gen).
 template <class K>
 constexpr bool kTableStaged = KindTraits<K>::NR * KindTraits<K>::N <= 32;
-constexpr int kTableRunFlagResiduals = 1, kTableRunFlagBsm = 2, kTableRunFlagCrs = 4;
 
 template <class K, bool kJac>
 __device__ __forceinline__ void TableStores(const GroupArgs& a, bool active, bool ok, int64_t gi,

@@ -10,32 +10,15 @@
 #include <stdint.h>
 
 #include "functors.hpp"
+#include "host_shared.hpp"  // kBlockThreads, kWave, kMaxSlots, PbDev, PackedRowDoubles
 #include "jet.hpp"
 #include "loss.hpp"
 
 namespace cse {
 
-constexpr int kBlockThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = kBlockThreads / kWave;
-constexpr int kMaxSlots = 10;  // parameter blocks per residual block (table path)
-
-
 // kImpossibleValue (internal/ceres/array_utils.h:52): the marker
 // AutoDifferentiate pre-fills outputs with.
 constexpr double kImpossibleValue = 1e302;
-
-// Device copy of a parameter block (table path).  plus_jacobian_offset:
-// >= 0 the explicit matrix, -1 none, kPlusJacobianQuaternion the
-// CSE_MANIFOLD_QUATERNION_EUCLIDEAN manifold (built in registers).
-constexpr int64_t kPlusJacobianQuaternion = -2;
-struct PbDev {
-  int64_t state_offset;
-  int64_t delta_offset;
-  int64_t plus_jacobian_offset;
-  int32_t tangent_size;
-  int32_t is_constant;
-};
 
 struct GroupArgs {
   int64_t n;
@@ -177,17 +160,6 @@ template <class K>
 struct AffineOnly<K, decltype((void)K::kAffineOnly)> {
   static constexpr bool value = K::kAffineOnly;
 };
-
-// Row stride (doubles) of the repacked slot-0 table that the LDS-DMA gather
-// reads: the block's size rounded up to 16 bytes and then to a power of two
-// up to 128 bytes, so that no row straddles a 128-byte L2 line (16 doubles
-// for the 9-double BAL camera).  Each DMA instruction then touches one line
-// per row instead of 1.5 on average: the residual-only evaluation of
-// problem-13682 went from 0.487 to 0.420 ms (profiles/round2/s4e).
-constexpr int PackedRowDoubles(int s) {
-  const int p = (s + 1) & ~1;
-  return p <= 2 ? 2 : p <= 4 ? 4 : p <= 8 ? 8 : p <= 16 ? 16 : p;
-}
 
 // Any of x[0..n) NaN or infinite?  An integer test on the exponent field:
 // the TU is compiled with -ffinite-math-only, which would fold isfinite().

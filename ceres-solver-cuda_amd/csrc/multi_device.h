@@ -20,15 +20,13 @@
 #include <string>
 
 #include "../../include/cse.h"
+#include "plan.hpp"  // CseFail, the shared descriptor validation
 
 struct CseMulti;
 
-// Records msg as the thread's last error (cse_last_error) and returns code.
-int CseFail(int code, const std::string& msg);
-// Residuals, parameter blocks and functor-data doubles per residual block of
-// a functor kind; false for an unknown kind (cse_evaluator.hip).
-bool CseKindShape(int kind, int* num_residuals, int* num_blocks, int* data_size);
-
+// A registered user functor kind's launch table and name, null for any other
+// kind (cse::UserLookup; the registry is in cse_evaluator.hip).
+const cse_functor_ops* CseUserKind(int kind, std::string* name);
 int MultiCreate(const cse_problem_desc* desc, const cse_options* options, const int32_t* devices,
                 int32_t num_devices, CseMulti** out);
 void MultiDestroy(CseMulti* m);

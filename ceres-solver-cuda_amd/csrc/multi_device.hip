@@ -339,10 +339,8 @@ int CreateShard(const cse_problem_desc* d, const cse_options* opts, CseMulti::Sh
     const Shape& k = shapes[gi];
     const cse_residual_group& g = d->groups[gi];
     const int64_t gg = g0 + l;
-    // The same checks as cse_create's: every range this shard hands back
-    // must lie inside the caller's buffers.
-    if (d->residual_layout[gg] < 0 || d->residual_layout[gg] + k.nr > d->num_residuals)
-      return CseFail(CSE_ERR_INVALID, "residual_layout out of range");
+    // Every range this shard hands back lies inside the caller's buffers
+    // (cse::ValidateGroups, MultiCreate).
     rb.Add(d->residual_layout[gg], d->residual_layout[gg] + k.nr);
     int a = 0;
     for (int j = 0; j < k.nb; ++j) {
@@ -350,12 +348,8 @@ int CreateShard(const cse_problem_desc* d, const cse_options* opts, CseMulti::Sh
       const cse_parameter_block& pb = d->parameter_blocks[pid];
       if (pb.is_constant || !has_layout) continue;
       const int64_t base = d->jacobian_per_residual_layout[gg] + (int64_t)a * k.nr;
-      if (base < 0 || base + k.nr > d->num_jacobian_per_residual_offsets)
-        return CseFail(CSE_ERR_INVALID, "jacobian_per_residual_layout out of range");
       for (int r = 0; r < k.nr; ++r) {
         const int64_t off = d->jacobian_per_residual_offsets[base + r];
-        if (off < 0 || off + pb.tangent_size > d->num_jacobian_values)
-          return CseFail(CSE_ERR_INVALID, "jacobian offset out of range");
         jb.Add(off, off + pb.tangent_size);
       }
       ++a;
@@ -443,21 +437,25 @@ int MultiCreate(const cse_problem_desc* d, const cse_options* options, const int
   if (options) opts = *options; else cse_default_options(&opts);
   if (opts.use_stream || opts.stream)
     return CseFail(CSE_ERR_INVALID, "cse_create_multi: streams are per device (use_stream must be 0)");
+  // The checks of cse_create: every index the sharding below follows is in
+  // range, and what a shard's own cse_create would refuse is refused here.
+  // They also give the groups' shapes.
   std::vector<Shape> shapes(d->num_groups);
+  {
+    cse::ProgramPlan checked;
+    const int rc = cse::ValidateGroups(d, &CseUserKind, &checked);
+    if (rc) return rc;
+    for (int gi = 0; gi < d->num_groups; ++gi)
+      shapes[gi] = {checked.shapes[gi].nr, checked.shapes[gi].nb, checked.shapes[gi].data};
+  }
   // Bucket key per global residual block: its last parameter block.
   std::vector<int64_t> key(d->num_residual_blocks);
   for (int64_t g = 0; g < d->num_residual_blocks; ++g) key[g] = -1 - g;
   for (int gi = 0; gi < d->num_groups; ++gi) {
     const cse_residual_group& g = d->groups[gi];
-    if (!CseKindShape(g.functor_kind, &shapes[gi].nr, &shapes[gi].nb, &shapes[gi].data))
-      return CseFail(CSE_ERR_UNSUPPORTED, "unknown functor kind " + std::to_string(g.functor_kind));
     const int nb = shapes[gi].nb;
     for (int64_t i = 0; i < g.num_blocks; ++i) {
       const int64_t gg = g.residual_block_index ? g.residual_block_index[i] : g.first_residual_block + i;
-      if (gg < 0 || gg >= d->num_residual_blocks)
-        return CseFail(CSE_ERR_INVALID, "residual block index out of range");
-      if (!g.parameter_block_ids)
-        return CseFail(CSE_ERR_INVALID, "group " + std::to_string(gi) + " arrays missing");
       key[gg] = g.parameter_block_ids[(int64_t)nb * i + nb - 1];
     }
   }
@@ -484,10 +482,6 @@ int MultiCreate(const cse_problem_desc* d, const cse_options* options, const int
       const int k = (int)(std::upper_bound(cuts.begin(), cuts.end(), gg) - cuts.begin()) - 1;
       for (int j = 0; j < nb; ++j) {
         const int32_t pid = g.parameter_block_ids[(int64_t)nb * i + j];
-        if (pid < 0 || pid >= d->num_parameter_blocks) {
-          delete m;
-          return CseFail(CSE_ERR_INVALID, "parameter block id out of range");
-        }
         used[k][pid] = 1;
         any[pid] = 1;
       }

@@ -85,15 +85,7 @@ __global__ __launch_bounds__(kBlockThreads) void GradientSlotKernel(const GradAr
   }
 }
 
-// Parameter blocks with many blocks (cameras): their block lists are cut
-// into chunks of at most kGradChunk blocks, one wave per chunk
-// (GradientLanesKernel), and GradientChunkReduceKernel adds each parameter
-// block's chunk partials in order.  Deterministic, no atomics.  (An
-// element-per-lane variant that reads whole cells per instruction measured
-// 3-10 % slower: the random cells and residual pairs cost whole lines
-// either way.)
-constexpr int kGradChunk = 512;
-
+// The chunks of a gradient plan (kGradChunk blocks at most, host_shared.hpp).
 struct GradChunks {
   const int64_t* begin;      // [nchunks + 1] chunk c covers perm[begin[c], begin[c+1])
   const int64_t* chunk_off;  // [count + 1] chunks of parameter block p
@@ -563,13 +555,7 @@ __global__ __launch_bounds__(kBlockThreads) void DtDxpyKernel(const double* D, c
 }
 
 // Program::Plus for manifold-free blocks: runs of consecutive state entries
-// whose delta offset is a constant shift away (one run for a BAL problem).
-struct PlusRun {
-  int64_t state_begin;
-  int64_t length;
-  int64_t delta_shift;  // delta index = state index - delta_shift
-};
-
+// whose delta offset is a constant shift away (PlusRun, host_shared.hpp).
 __global__ __launch_bounds__(kBlockThreads) void PlusKernel(const double* x, const double* delta,
                                                             double* out, const PlusRun* runs,
                                                             int num_runs) {
@@ -587,14 +573,7 @@ __global__ __launch_bounds__(kBlockThreads) void PlusKernel(const double* x, con
 // per thread: ProductManifold<QuaternionManifold, EuclideanManifold<n>>::Plus,
 // i.e. QuaternionPlusImpl (internal/ceres/manifold.cc:28-59: the quaternion
 // exp(delta) on the left of x, x unchanged when |delta| is zero) and x + delta
-// for the Euclidean tail.
-struct QuatPlusBlock {
-  int64_t state_offset;
-  int64_t delta_offset;
-  int32_t size;
-  int32_t pad;
-};
-
+// for the Euclidean tail (QuatPlusBlock, host_shared.hpp).
 __global__ __launch_bounds__(kBlockThreads) void QuaternionPlusKernel(const double* x,
                                                                       const double* delta,
                                                                       double* out,

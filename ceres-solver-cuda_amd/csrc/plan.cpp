@@ -1,0 +1,891 @@
+// plan.cpp -- the host-only planner behind cse_create (plan.hpp).
+//
+// Pure host logic over a cse_problem_desc: no HIP, no device memory.  The
+// caller validates first (Validate, ValidateGroups); the planning functions
+// index the descriptor's arrays without further checks.
+#include "plan.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <utility>
+
+namespace cse {
+std::string& LastError();  // layout.cpp: one per thread, shared by every entry point
+}  // namespace cse
+
+int CseFail(int code, const std::string& msg) {
+  cse::LastError() = msg;
+  return code;
+}
+
+namespace cse {
+
+namespace {
+
+int Fail(int code, const std::string& msg) { return CseFail(code, msg); }
+
+// Gradient post-pass kernels of the built-in shapes; a user kind brings its
+// own (cse_functor_ops.gradient).
+bool GradSupported(int nr, int size, const cse_functor_ops* user, int slot) {
+  if (user) return user->gradient[slot] != nullptr;
+  return (nr == 2 && (size == 9 || size == 3 || size == 7 || size == 10)) || (nr == 3 && size == 3);
+}
+
+int64_t BlockIndex(const cse_residual_group& g, int64_t i) {
+  return g.residual_block_index ? g.residual_block_index[i] : g.first_residual_block + i;
+}
+
+}  // namespace
+
+bool ShapeOf(int kind, const cse_functor_ops* user, KindShape* k) {
+  *k = KindShape{};
+  if (user) {
+    k->nr = user->num_residuals;
+    k->nb = user->num_parameter_blocks;
+    k->data = user->data_size;
+    for (int j = 0; j < k->nb; ++j) k->sz[j] = user->parameter_block_sizes[j];
+    k->x0 = k->sz[0];
+  } else {
+    const KindRow* r = KindRowOf(kind);
+    if (!r) return false;
+    k->nr = r->nr;
+    k->nb = r->nb;
+    k->data = r->data;
+    for (int j = 0; j < r->nb; ++j) k->sz[j] = r->sz[j];
+    k->x0 = r->x0;
+  }
+  k->s0 = k->sz[0];
+  k->s1 = k->nb > 1 ? k->sz[1] : 0;
+  return true;
+}
+
+bool UserAffine(const cse_functor_ops* u) {
+  bool all = true;
+  for (int c = 0; c < 2; ++c)
+    for (int j = 0; j < 2; ++j)
+      for (int d = 0; d < 2; ++d) all = all && u->affine[c][j][d] != nullptr;
+  return all;
+}
+
+bool UserFused(const cse_functor_ops* user, const KindShape& k) {
+  return user && user->fused_points[0] && user->fused_points[1] && user->camera_gradient &&
+         k.nb == 2 && k.s1 == 3 && k.s0 >= 1 && k.s0 <= 16;
+}
+
+int Validate(const cse_problem_desc* d) {
+  if (!d) return Fail(CSE_ERR_INVALID, "null descriptor");
+  if (d->abi_version != CSE_ABI_VERSION)
+    return Fail(CSE_ERR_INVALID, "abi_version mismatch: descriptor " +
+                                     std::to_string(d->abi_version) + ", library " +
+                                     std::to_string(CSE_ABI_VERSION));
+  if (d->num_groups < 0 || (d->num_groups > 0 && !d->groups))
+    return Fail(CSE_ERR_INVALID, "bad groups");
+  if (d->num_parameter_blocks < 0 || (d->num_parameter_blocks > 0 && !d->parameter_blocks))
+    return Fail(CSE_ERR_INVALID, "bad parameter blocks");
+  for (int64_t b = 0; b < d->num_parameter_blocks; ++b) {
+    const cse_parameter_block& pb = d->parameter_blocks[b];
+    if (pb.size <= 0 || pb.tangent_size < 0 || pb.tangent_size > pb.size)
+      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) + " has bad size");
+    const int64_t lim = pb.is_constant ? d->num_constant_parameters : d->num_parameters;
+    if (pb.state_offset < 0 || pb.state_offset + pb.size > lim)
+      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) + " state out of range");
+    if (!pb.is_constant && (pb.delta_offset < 0 ||
+                            pb.delta_offset + pb.tangent_size > d->num_effective_parameters))
+      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) + " delta out of range");
+    if (pb.plus_jacobian_offset >= 0 &&
+        pb.plus_jacobian_offset + (int64_t)pb.size * pb.tangent_size > d->num_plus_jacobian_values)
+      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) +
+                                       " plus jacobian out of range");
+    if (pb.manifold != CSE_MANIFOLD_MATRIX && pb.manifold != CSE_MANIFOLD_QUATERNION_EUCLIDEAN)
+      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) + ": unknown manifold " +
+                                       std::to_string(pb.manifold));
+    if (pb.manifold == CSE_MANIFOLD_QUATERNION_EUCLIDEAN &&
+        (pb.size < 4 || pb.tangent_size != pb.size - 1 || pb.plus_jacobian_offset >= 0))
+      return Fail(CSE_ERR_INVALID, "parameter block " + std::to_string(b) +
+                                       ": the quaternion manifold needs size >= 4, tangent_size "
+                                       "size - 1 and plus_jacobian_offset -1");
+  }
+  if (d->num_constant_parameters > 0 && !d->constant_state)
+    return Fail(CSE_ERR_INVALID, "constant_state missing");
+  if (d->num_plus_jacobian_values > 0 && !d->plus_jacobians)
+    return Fail(CSE_ERR_INVALID, "plus_jacobians missing");
+  if (d->num_residual_blocks < 0 || !d->residual_layout)
+    return Fail(CSE_ERR_INVALID, "residual_layout missing");
+  return CSE_OK;
+}
+
+int ValidateGroups(const cse_problem_desc* d, UserLookup lookup, ProgramPlan* P) {
+  *P = ProgramPlan{};
+  P->has_layout = d->jacobian_per_residual_layout && d->jacobian_per_residual_offsets;
+  P->shapes.resize((size_t)d->num_groups);
+  P->users.assign((size_t)d->num_groups, nullptr);
+  P->user_names.resize((size_t)d->num_groups);
+  P->owner.assign((size_t)d->num_parameter_blocks, -1);
+  int64_t covered_res = 0, covered_jac = 0;
+  std::vector<char> seen((size_t)d->num_parameter_blocks, 0);
+  for (int gi = 0; gi < d->num_groups; ++gi) {
+    const cse_residual_group& g = d->groups[gi];
+    KindShape& k = P->shapes[gi];
+    const cse_functor_ops* user =
+        lookup && g.functor_kind >= 0 ? lookup(g.functor_kind, &P->user_names[gi]) : nullptr;
+    if (g.functor_kind < 0 || !ShapeOf(g.functor_kind, user, &k))
+      return Fail(CSE_ERR_UNSUPPORTED, "unknown functor kind " + std::to_string(g.functor_kind));
+    if (g.loss.kind < CSE_LOSS_TRIVIAL || g.loss.kind > CSE_LOSS_USER)
+      return Fail(CSE_ERR_UNSUPPORTED, "unknown loss kind " + std::to_string(g.loss.kind));
+    if (IsTestKind(g.functor_kind) && (g.loss.kind != CSE_LOSS_TRIVIAL || g.loss.scaled))
+      return Fail(CSE_ERR_UNSUPPORTED, "test functor kinds take the trivial loss only");
+    P->users[gi] = user;
+    if (user) {
+      // The kernels of a user kind apply the loss they were built with
+      // (AutoDiffResidualBlockCUDAEvaluator<F, LossFunctionCUDA, ...>).
+      if (g.loss.kind != user->loss_kind)
+        return Fail(CSE_ERR_INVALID, "group " + std::to_string(gi) + ": user functor kind " +
+                                         P->user_names[gi] + " was registered with loss kind " +
+                                         std::to_string(user->loss_kind) + ", the group has " +
+                                         std::to_string(g.loss.kind));
+    } else if (g.loss.kind == CSE_LOSS_USER) {
+      return Fail(CSE_ERR_INVALID, "the user loss kind (3) needs a user functor kind registered with it");
+    }
+    if (g.num_blocks < 0 || (g.num_blocks > 0 && (!g.parameter_block_ids || !g.functor_data)))
+      return Fail(CSE_ERR_INVALID, "group " + std::to_string(gi) + " arrays missing");
+    for (int64_t i = 0; i < g.num_blocks; ++i) {
+      const int64_t gidx = BlockIndex(g, i);
+      if (gidx < 0 || gidx >= d->num_residual_blocks)
+        return Fail(CSE_ERR_INVALID, "residual block index out of range in group " + std::to_string(gi));
+      if (d->residual_layout[gidx] < 0 || d->residual_layout[gidx] + k.nr > d->num_residuals)
+        return Fail(CSE_ERR_INVALID, "residual_layout out of range");
+      covered_res += k.nr;
+      for (int j = 0; j < k.nb; ++j) {
+        const int32_t id = g.parameter_block_ids[i * k.nb + j];
+        if (id < 0 || id >= d->num_parameter_blocks)
+          return Fail(CSE_ERR_INVALID, "parameter block id out of range in group " + std::to_string(gi));
+        const int want = k.sz[j];
+        const cse_parameter_block& pb = d->parameter_blocks[id];
+        if (pb.size != want)
+          return Fail(CSE_ERR_INVALID, "parameter block size does not match the functor");
+        if (!pb.is_constant) covered_jac += (int64_t)k.nr * pb.tangent_size;
+        const int32_t tag = 2 * gi + j;
+        if (P->owner[id] == -1) P->owner[id] = tag;
+        else if (P->owner[id] != tag) P->owner[id] = -2;
+        if (!seen[id]) {
+          seen[id] = 1;
+          P->bytes_jac += 8LL * pb.size;
+          P->bytes_res += 8LL * pb.size;
+        }
+      }
+      if (P->has_layout) {
+        const int64_t base = d->jacobian_per_residual_layout[gidx];
+        int na = 0;
+        for (int j = 0; j < k.nb; ++j)
+          if (!d->parameter_blocks[g.parameter_block_ids[i * k.nb + j]].is_constant) ++na;
+        if (base < 0 || base + (int64_t)na * k.nr > d->num_jacobian_per_residual_offsets)
+          return Fail(CSE_ERR_INVALID, "jacobian_per_residual_layout out of range");
+        int a = 0;
+        for (int j = 0; j < k.nb; ++j) {
+          const cse_parameter_block& pb = d->parameter_blocks[g.parameter_block_ids[i * k.nb + j]];
+          if (pb.is_constant) continue;
+          for (int r = 0; r < k.nr; ++r) {
+            const int64_t off = d->jacobian_per_residual_offsets[base + a * k.nr + r];
+            if (off < 0 || off + pb.tangent_size > d->num_jacobian_values)
+              return Fail(CSE_ERR_INVALID, "jacobian offset out of range");
+          }
+          ++a;
+        }
+      }
+    }
+    const int64_t per_block = 8LL * k.data + 4LL * k.nb + 8LL * k.nr;
+    P->bytes_res += per_block * g.num_blocks;
+    P->bytes_jac += per_block * g.num_blocks;
+  }
+  P->bytes_jac += 8LL * covered_jac;
+  P->res_covered = covered_res == d->num_residuals;
+  P->jac_covered = covered_jac == d->num_jacobian_values;
+  return CSE_OK;
+}
+
+// CameraGradientKernel's passes: its point gathers (slot 1, a table of
+// 8 s1 bytes per point) hit the Infinity Cache only while the table plus
+// every byte streamed between two uses of a line fits in ~256 MiB
+// (MI355X_MICROARCH.md, Infinity Cache).  In camera order a point's blocks
+// are spread over the whole launch, between which the sorted functor data
+// and slot-1 ids (8 data + 4 bytes a block) stream by: 107 + 580 MB at
+// problem-13682.  Cut into passes of consecutive point ranges, taken one
+// after the other, each pass touches 1/passes of both: passes = the total
+// over kCamGradPassBytes, at most 64.  (Passes 8 times finer dealt to the
+// XCDs measured no faster.)  The camera sums over written contributions
+// (gradient_mode 3, the Schur and CGNR operators' F^T u) take the same
+// plan's chunks pass-major too (GradientContribKernel's order).
+constexpr double kCamGradPassBytes = 96e6;
+int CamGradPasses(const cse_residual_group& g, const KindShape& k) {
+  int32_t lo = INT32_MAX, hi = INT32_MIN;
+  for (int64_t i = 0; i < g.num_blocks; ++i) {
+    lo = std::min(lo, g.parameter_block_ids[i * k.nb + 1]);
+    hi = std::max(hi, g.parameter_block_ids[i * k.nb + 1]);
+  }
+  if (g.num_blocks == 0) return 1;
+  const double bytes = 8.0 * k.s1 * ((double)hi - lo + 1) + (8.0 * k.data + 4.0) * g.num_blocks;
+  const int p = (int)std::ceil(bytes / kCamGradPassBytes);
+  return std::max(1, std::min(64, p));
+}
+
+// Blocks of slot j listed per parameter block (stable counting sort): the
+// gradient post-pass sums each parameter block's blocks in this order.
+// cpb (may be null): the descriptor's parameter blocks; blocks whose slot-j
+// parameter block is constant are left out (a held camera has no gradient
+// row), which makes the plan a permutation of the other blocks only.
+// passes > 1 (slot 0 of a two-slot kind): each parameter block's list is
+// further ordered by pass, pass(i) = i * passes / n (block order: in a
+// Schur-ordered problem, consecutive point ranges), and no chunk straddles
+// two passes; chunk_order lists the chunks pass-major, the order in which
+// CameraGradientKernel takes them (CamGradPasses).
+void BuildGradPlan(const cse_residual_group& g, const KindShape& k, int j, GradPlanInfo* plan,
+                   GradTables* tables, const cse_parameter_block* cpb, int passes) {
+  const int64_t n = g.num_blocks;
+  *plan = GradPlanInfo{};
+  *tables = GradTables{};
+  if (passes < 1 || n < passes) passes = 1;
+  auto skip = [&](int64_t i) {
+    return cpb && cpb[g.parameter_block_ids[i * k.nb + j]].is_constant;
+  };
+  auto pass_of = [&](int64_t i) { return (int)((__int128)i * passes / n); };
+  int32_t lo = g.parameter_block_ids[j], hi = lo;
+  for (int64_t i = 0; i < n; ++i) {
+    lo = std::min(lo, g.parameter_block_ids[i * k.nb + j]);
+    hi = std::max(hi, g.parameter_block_ids[i * k.nb + j]);
+  }
+  const int64_t count = (int64_t)hi - lo + 1;
+  // Counting sort on (parameter block, pass): poff[p * passes + t].
+  std::vector<int64_t> poff(count * passes + 1, 0);
+  bool sorted = true;
+  int64_t kept = 0, prev = INT64_MIN;
+  for (int64_t i = 0; i < n; ++i) {
+    if (skip(i)) {
+      sorted = false;  // a permutation of the kept blocks, never the identity
+      continue;
+    }
+    const int32_t id = g.parameter_block_ids[i * k.nb + j];
+    ++poff[(id - lo) * passes + pass_of(i) + 1];
+    if (id < prev) sorted = false;
+    prev = id;
+    ++kept;
+  }
+  plan->nperm = kept;
+  for (int64_t p = 0; p < count * passes; ++p) poff[p + 1] += poff[p];
+  std::vector<int64_t>& off = tables->off;
+  off.resize(count + 1);
+  for (int64_t p = 0; p <= count; ++p) off[p] = poff[p * passes];
+  plan->all_present = true;
+  for (int64_t p = 0; p < count && plan->all_present; ++p) plan->all_present = off[p + 1] > off[p];
+  plan->sorted = sorted;
+  plan->lo = lo;
+  plan->count = count;
+  plan->wave = !sorted && n >= 32 * count;  // on average 32+ blocks per parameter block
+  if (!sorted) {
+    std::vector<int32_t>& perm = tables->perm;
+    perm.resize(std::max<int64_t>(kept, 1));
+    std::vector<int64_t> next(poff.begin(), poff.end() - 1);
+    for (int64_t i = 0; i < n; ++i)
+      if (!skip(i))
+        perm[next[(g.parameter_block_ids[i * k.nb + j] - lo) * passes + pass_of(i)]++] = (int32_t)i;
+    // Chunks: the wave-mode post-pass and the fused gradient's slot-0 pass.
+    std::vector<int64_t>& begin = tables->chunk_begin;
+    std::vector<int64_t>& coff = tables->chunk_off;
+    std::vector<int32_t>& chunk_pb = tables->chunk_pb;
+    std::vector<int32_t> cpass;
+    coff.assign(count + 1, 0);
+    for (int64_t p = 0; p < count; ++p) {
+      coff[p] = (int64_t)begin.size();
+      for (int t = 0; t < passes; ++t)
+        for (int64_t q = poff[p * passes + t]; q < poff[p * passes + t + 1]; q += kGradChunk) {
+          begin.push_back(q);
+          chunk_pb.push_back((int32_t)(lo + p));
+          cpass.push_back(t);
+        }
+    }
+    coff[count] = (int64_t)begin.size();
+    plan->nchunks = (int64_t)begin.size();
+    plan->passes = passes;
+    if (passes > 1) {  // pass-major launch order, camera order within a pass
+      std::vector<int32_t>& order = tables->chunk_order;
+      order.reserve(begin.size());
+      for (int t = 0; t < passes; ++t)
+        for (int64_t c = 0; c < plan->nchunks; ++c)
+          if (cpass[c] == t) order.push_back((int32_t)c);
+    }
+    // Chunk c covers [begin[c], begin[c + 1]): a parameter block's last
+    // chunk ends at off[p + 1], where the next non-empty one starts.
+    begin.push_back(kept);
+  }
+  plan->ready = true;
+}
+
+namespace {
+
+// Is the group table-free?  Returns the Policy (see evaluate_kernel.hpp
+// for the two affine shapes) and fills G's affine parameters; with constant
+// slot-0 blocks also T->fbase.
+int DetectAffine(const cse_problem_desc* d, const cse_residual_group& g, const KindShape& k,
+                 GroupPlan* G, GroupTables* T) {
+  const int64_t n = g.num_blocks;
+  if (n == 0) return kTable;
+  // The affine kernels take one or two slots, at most three residuals; a
+  // user kind has them only for the shapes its header instantiates.
+  if (k.nb > 2 || k.nr > 3 || IsTestKind(g.functor_kind)) return kTable;
+  if (G->user && !UserAffine(G->user)) return kTable;
+  auto gidx = [&](int64_t i) { return BlockIndex(g, i); };
+  // Ambient sizes (state offsets) and tangent sizes (delta offsets, the
+  // Jacobian's columns).  Slot 0 of the quaternion camera may be on
+  // CSE_MANIFOLD_QUATERNION_EUCLIDEAN (then in every block): the kernel kind
+  // becomes kKindQuaternionTangent, which builds the plus-Jacobian itself.
+  const int ambient[2] = {k.s0, k.s1};
+  int sizes[2] = {k.s0, k.s1};
+  int manifold[2] = {CSE_MANIFOLD_MATRIX, CSE_MANIFOLD_MATRIX};
+  // The first block whose slot j is active (bases and the manifold come from it).
+  int64_t first[2] = {-1, -1};
+  for (int64_t i = 0; i < n && (first[0] < 0 || (k.nb > 1 && first[1] < 0)); ++i)
+    for (int j = 0; j < k.nb; ++j)
+      if (first[j] < 0 && !d->parameter_blocks[g.parameter_block_ids[i * k.nb + j]].is_constant)
+        first[j] = i;
+  for (int j = 0; j < k.nb; ++j)
+    if (first[j] < 0) return kTable;
+  if (g.functor_kind == CSE_FUNCTOR_SNAVELY_QUATERNION_2_10_3 &&
+      d->parameter_blocks[g.parameter_block_ids[first[0] * k.nb]].manifold ==
+          CSE_MANIFOLD_QUATERNION_EUCLIDEAN) {
+    manifold[0] = CSE_MANIFOLD_QUATERNION_EUCLIDEAN;
+    sizes[0] = k.s0 - 1;
+  }
+  G->slot0_manifold = manifold[0];
+  // Constant slot-0 blocks (a held camera) are allowed for the kinds with the
+  // constant-aware kernels (the 9-column cameras, cse::ShippedTuneC0).
+  const bool const0_ok = k.nb == 2 && (g.functor_kind == CSE_FUNCTOR_SNAVELY_2_9_3 ||
+                                       manifold[0] == CSE_MANIFOLD_QUATERNION_EUCLIDEAN);
+  // Parameters: active (slot 0 may be constant, above), no explicit
+  // plus-Jacobian, state/delta offsets affine in the id.
+  for (int j = 0; j < k.nb; ++j) {
+    const int32_t id0 = g.parameter_block_ids[first[j] * k.nb + j];
+    const cse_parameter_block& pb0 = d->parameter_blocks[id0];
+    G->state_base[j] = pb0.state_offset - (int64_t)ambient[j] * id0;
+    G->delta_base[j] = pb0.delta_offset - (int64_t)sizes[j] * id0;
+  }
+  // With constant slot-0 blocks the active ones need not be affine either
+  // (a held camera in the middle shifts the later ones' offsets): their values
+  // come through the repacked table, their gradient rows through a table.
+  G->const0 = false;
+  for (int64_t i = 0; i < n && !G->const0; ++i)
+    G->const0 = d->parameter_blocks[g.parameter_block_ids[i * k.nb]].is_constant != 0;
+  if (G->const0 && !const0_ok) return kTable;
+  for (int64_t i = 0; i < n; ++i)
+    for (int j = 0; j < k.nb; ++j) {
+      const int32_t id = g.parameter_block_ids[i * k.nb + j];
+      const cse_parameter_block& pb = d->parameter_blocks[id];
+      if (pb.is_constant) {
+        if (j != 0 || pb.size != ambient[0]) return kTable;
+        continue;
+      }
+      if (pb.plus_jacobian_offset >= 0 || pb.manifold != manifold[j] ||
+          pb.tangent_size != sizes[j] || pb.size != ambient[j])
+        return kTable;
+      if (j == 0 && G->const0) continue;
+      if (pb.state_offset != G->state_base[j] + (int64_t)ambient[j] * id) return kTable;
+      if (pb.delta_offset != G->delta_base[j] + (int64_t)sizes[j] * id) return kTable;
+    }
+  // Slot-0 id range (the repacked table of the cooperative gather).
+  int32_t lo = g.parameter_block_ids[0], hi = lo;
+  for (int64_t i = 0; i < n; ++i) {
+    lo = std::min(lo, g.parameter_block_ids[i * k.nb]);
+    hi = std::max(hi, g.parameter_block_ids[i * k.nb]);
+  }
+  G->slot0_lo = lo;
+  G->slot0_count = (int64_t)hi - lo + 1;
+  G->slot0_stride = (sizes[0] + 1) & ~1;  // per-block slot-0 gradient contributions
+  G->packed_stride = PackedRowDoubles(ambient[0]);
+  // Residuals.
+  G->res_base = d->residual_layout[gidx(0)];
+  for (int64_t i = 0; i < n; ++i)
+    if (d->residual_layout[gidx(i)] != G->res_base + (int64_t)k.nr * i) return kTable;
+  // Jacobian rows.
+  if (!d->jacobian_per_residual_layout || !d->jacobian_per_residual_offsets) return kAffinePacked;
+  const int64_t* L = d->jacobian_per_residual_layout;
+  const int64_t* O = d->jacobian_per_residual_offsets;
+  if (G->const0) {
+    const int NR = k.nr, S0 = sizes[0], S1 = sizes[1];
+    auto act = [&](int64_t i) {
+      return !d->parameter_blocks[g.parameter_block_ids[i * k.nb]].is_constant;
+    };
+    const int64_t nchunks = (n + kWave - 1) / kWave;
+    // BlockSparseMatrix: the E (slot 1) cells affine, kR x S1 packed at
+    // e0 + kR*S1*i; the F cells of the blocks with an active camera packed in
+    // block order from f0 (a constant camera has none; its block's first
+    // active entries are the E rows).  Per chunk of 64 blocks: its first F
+    // cell, then the end of the F cells.
+    auto try_bsm = [&]() -> bool {
+      const int64_t f0 = O[L[gidx(first[0])]];
+      const int64_t e0 = O[L[gidx(0)] + (act(0) ? NR : 0)];
+      std::vector<int64_t> fb;
+      fb.reserve((size_t)nchunks + 1);
+      int64_t rank = 0;
+      for (int64_t i = 0; i < n; ++i) {
+        if (i % kWave == 0) fb.push_back(f0 + (int64_t)NR * S0 * rank);
+        const int64_t base = L[gidx(i)];
+        int a = 0;
+        if (act(i)) {
+          for (int r = 0; r < NR; ++r)
+            if (O[base + r] != f0 + (int64_t)NR * S0 * rank + (int64_t)r * S0) return false;
+          ++rank;
+          a = 1;
+        }
+        for (int r = 0; r < NR; ++r)
+          if (O[base + a * NR + r] != e0 + (int64_t)NR * S1 * i + (int64_t)r * S1) return false;
+      }
+      for (int r = 0; r < NR; ++r) {
+        G->jac_base[0][r] = f0 + (int64_t)r * S0;
+        G->jac_base[1][r] = e0 + (int64_t)r * S1;
+      }
+      G->jac_stride[0] = (int64_t)NR * S0;
+      G->jac_stride[1] = (int64_t)NR * S1;
+      fb.push_back(f0 + (int64_t)NR * S0 * rank);
+      T->fbase = std::move(fb);
+      return true;
+    };
+    // CompressedRowSparseMatrix (compressed_row_jacobian_writer.cc:145-185):
+    // every block's rows packed in block order, NR x (S0 + S1) with an active
+    // camera (camera and point at fixed columns of the row) and NR x S1 with
+    // a held one (the point alone).  Per chunk: the offset of its first row,
+    // then the end.
+    auto try_crs = [&]() -> bool {
+      const int N = S0 + S1;
+      const int64_t b0 = L[gidx(first[0])];
+      const int64_t cam0 = O[b0], pt0 = O[b0 + NR];
+      const int64_t rb0 = std::min(cam0, pt0);
+      const int camcol = (int)(cam0 - rb0), ptcol = (int)(pt0 - rb0);
+      if (!((camcol == 0 && ptcol == S0) || (ptcol == 0 && camcol == S1))) return false;
+      const int64_t r0 = rb0 - (int64_t)NR * S1 * first[0];
+      std::vector<int64_t> cb;
+      cb.reserve((size_t)nchunks + 1);
+      int64_t pos = r0;
+      for (int64_t i = 0; i < n; ++i) {
+        if (i % kWave == 0) cb.push_back(pos);
+        const int64_t base = L[gidx(i)];
+        if (act(i)) {
+          for (int r = 0; r < NR; ++r)
+            if (O[base + r] != pos + (int64_t)r * N + camcol ||
+                O[base + NR + r] != pos + (int64_t)r * N + ptcol)
+              return false;
+          pos += (int64_t)NR * N;
+        } else {
+          for (int r = 0; r < NR; ++r)
+            if (O[base + r] != pos + (int64_t)r * S1) return false;
+          pos += (int64_t)NR * S1;
+        }
+      }
+      cb.push_back(pos);
+      for (int r = 0; r < NR; ++r) {
+        G->jac_base[0][r] = r0 + (int64_t)r * N + camcol;
+        G->jac_base[1][r] = r0 + (int64_t)r * N + ptcol;
+      }
+      G->jac_stride[0] = G->jac_stride[1] = (int64_t)NR * N;
+      T->fbase = std::move(cb);
+      return true;
+    };
+    if (try_bsm()) return kAffinePacked;
+    if (try_crs()) return kAffineCrs;
+    return kTable;
+  }
+  for (int j = 0; j < k.nb; ++j)
+    for (int r = 0; r < k.nr; ++r) G->jac_base[j][r] = O[L[gidx(0)] + j * k.nr + r];
+  for (int j = 0; j < k.nb; ++j)
+    G->jac_stride[j] = n > 1 ? O[L[gidx(1)] + j * k.nr] - G->jac_base[j][0] : (int64_t)k.nr * sizes[j];
+  for (int64_t i = 0; i < n; ++i)
+    for (int j = 0; j < k.nb; ++j)
+      for (int r = 0; r < k.nr; ++r)
+        if (O[L[gidx(i)] + j * k.nr + r] != G->jac_base[j][r] + G->jac_stride[j] * i) return kTable;
+  const int N = sizes[0] + sizes[1];
+  // Shape 1: packed cells (BlockSparseMatrix).
+  bool packed = true;
+  for (int j = 0; j < k.nb; ++j) {
+    if (G->jac_stride[j] != (int64_t)k.nr * sizes[j]) packed = false;
+    for (int r = 0; r < k.nr; ++r)
+      if (G->jac_base[j][r] != G->jac_base[j][0] + (int64_t)r * sizes[j]) packed = false;
+  }
+  if (packed && !(G->jac_stride[0] == (int64_t)k.nr * N && k.nb > 1)) return kAffinePacked;
+  // Shape 2: interleaved rows (CompressedRowSparseMatrix): every slot has
+  // stride kR*N, row r of the block starts at row0 + r*N and each slot sits
+  // at a fixed column position inside the row, the slots tiling [0, N).
+  int64_t row0 = G->jac_base[0][0];
+  for (int j = 0; j < k.nb; ++j) row0 = std::min(row0, G->jac_base[j][0]);
+  bool cover[32] = {false};
+  for (int j = 0; j < k.nb; ++j) {
+    if (G->jac_stride[j] != (int64_t)k.nr * N) return kTable;
+    const int64_t col = G->jac_base[j][0] - row0;
+    if (col < 0 || col + sizes[j] > N) return kTable;
+    for (int c = 0; c < sizes[j]; ++c) {
+      if (cover[col + c]) return kTable;
+      cover[col + c] = true;
+    }
+    for (int r = 0; r < k.nr; ++r)
+      if (G->jac_base[j][r] != row0 + (int64_t)r * N + col) return kTable;
+  }
+  return kAffineCrs;
+}
+
+// The tables of a group with constant slot-0 blocks: per id of the slot-0
+// range its active bit, repack source and delta offset, and per chunk the
+// previous chunk with F cells (BSM) or row blocks (CRS).
+void BuildConst0Tables(const cse_problem_desc* d, const GroupPlan& G, GroupTables* T) {
+  const KindShape& k = G.shape;
+  T->bits.assign((size_t)((G.slot0_count + 31) / 32), 0u);
+  T->src.assign((size_t)G.slot0_count, 0);
+  T->dlt.assign((size_t)G.slot0_count, -1);
+  // Ids in the range that are not camera-sized rows in bounds (blocks no
+  // block of the group uses) repack the first active camera (never read).
+  const int64_t fallback = G.state_base[0] + (int64_t)k.x0 * G.slot0_lo;  // overwritten below
+  int64_t first_active = -1;
+  for (int64_t q = 0; q < G.slot0_count && first_active < 0; ++q) {
+    const cse_parameter_block& pb = d->parameter_blocks[G.slot0_lo + q];
+    if (!pb.is_constant && pb.size == k.x0) first_active = pb.state_offset;
+  }
+  for (int64_t q = 0; q < G.slot0_count; ++q) {
+    const cse_parameter_block& pb = d->parameter_blocks[G.slot0_lo + q];
+    const bool fits = pb.size == k.x0 && pb.state_offset >= 0 &&
+                      pb.state_offset + k.x0 <= (pb.is_constant ? d->num_constant_parameters
+                                                                : d->num_parameters);
+    if (!fits) {
+      T->src[q] = first_active >= 0 ? first_active : fallback;
+    } else if (pb.is_constant) {
+      T->src[q] = -1 - pb.state_offset;
+    } else {
+      T->bits[q >> 5] |= 1u << (q & 31);
+      T->src[q] = pb.state_offset;
+      T->dlt[q] = pb.delta_offset;
+    }
+  }
+  if (!T->fbase.empty()) {
+    const int64_t nchunks = (int64_t)T->fbase.size() - 1;
+    T->prev_seg.assign((size_t)nchunks, -1);
+    int32_t last = -1;
+    for (int64_t c = 0; c < nchunks; ++c) {
+      T->prev_seg[c] = last;
+      if (T->fbase[c + 1] > T->fbase[c]) last = (int32_t)c;
+    }
+  }
+}
+
+// A table group whose slot-0 blocks are all plain: active, no manifold
+// (plus_jacobian_offset -1), tangent size = size = the kind's, state and
+// delta offsets affine in the id.  EvaluateTableKernel then forms their PbDev
+// records instead of loading them: one cache line less per lane for a
+// camera-like slot 0, whose lines the point stream evicts from L2 between
+// uses.
+void DetectPlain0(const cse_problem_desc* d, const cse_residual_group& g, GroupPlan* G) {
+  const KindShape& k = G->shape;
+  G->plain0 = false;
+  if (G->affine || G->n == 0) return;
+  const int S = k.sz[0];
+  const int32_t id0 = g.parameter_block_ids[0];
+  const int64_t sb = d->parameter_blocks[id0].state_offset - (int64_t)S * id0;
+  const int64_t db = d->parameter_blocks[id0].delta_offset - (int64_t)S * id0;
+  for (int64_t i = 0; i < G->n; ++i) {
+    const int32_t id = g.parameter_block_ids[i * k.nb];
+    const cse_parameter_block& p = d->parameter_blocks[id];
+    if (p.is_constant || p.manifold != CSE_MANIFOLD_MATRIX || p.plus_jacobian_offset != -1 ||
+        p.size != S || p.tangent_size != S || p.state_offset != sb + (int64_t)S * id ||
+        p.delta_offset != db + (int64_t)S * id)
+      return;
+  }
+  G->plain0 = true;
+  G->plain0_state_base = sb;
+  G->plain0_delta_base = db;
+  // A plain slot 0 of a small id range (the cameras) is read from a
+  // repacked copy, as the affine kernels read it (RepackSlot0Kernel, every
+  // evaluation): one 128-byte row a lane instead of its values at an
+  // 8-byte alignment.
+  int32_t lo = INT32_MAX, hi = INT32_MIN;
+  for (int64_t i = 0; i < g.num_blocks; ++i) {
+    lo = std::min(lo, g.parameter_block_ids[i * k.nb]);
+    hi = std::max(hi, g.parameter_block_ids[i * k.nb]);
+  }
+  const int64_t count = (int64_t)hi - lo + 1;
+  if (k.sz[0] <= 16 && count <= (1 << 20)) {
+    G->repack0 = true;
+    G->slot0_lo = lo;
+    G->slot0_count = count;
+    G->packed_stride = PackedRowDoubles(k.sz[0]);
+    G->state_base[0] = G->plain0_state_base;
+  }
+}
+
+// The general kernel's store runs, found once per 64-block chunk (the
+// wave's blocks) by the tests TableStores makes on the device: flags
+// kTableRunFlagResiduals when the chunk's residuals are one run (NR apart),
+// kTableRunFlagBsm / Crs when every slot is active in all or none of its
+// blocks with one tangent size and its Jacobian rows form BlockSparseMatrix
+// cell runs / CompressedRow row blocks; then the residual run's start and
+// each active slot's first row.  [chunks][2 + nb]; shapes the kernel stages
+// (kTableStaged: NR x N <= 32) only.
+void BuildTableRuns(const cse_problem_desc* d, const cse_residual_group& g, const GroupPlan& G,
+                    bool has_layout, std::vector<int64_t>* out) {
+  const KindShape& k = G.shape;
+  int N = 0;
+  for (int j = 0; j < k.nb; ++j) N += k.sz[j];
+  if (G.affine || G.n == 0 || k.nr * N > 32) return;
+  const int NB = k.nb, NR = k.nr, W = 2 + NB;
+  const int64_t n = G.n, nch = (n + kWave - 1) / kWave;
+  std::vector<int64_t>& runs = *out;
+  runs.assign((size_t)(nch * W), 0);
+  auto gidx = [&](int64_t i) { return BlockIndex(g, i); };
+  auto pb = [&](int64_t i, int j) -> const cse_parameter_block& {
+    return d->parameter_blocks[g.parameter_block_ids[i * NB + j]];
+  };
+  for (int64_t c = 0; c < nch; ++c) {
+    const int64_t i0 = c * kWave;
+    const int nb = (int)std::min<int64_t>(kWave, n - i0);
+    int64_t* R = &runs[(size_t)(c * W)];
+    const int64_t off0 = d->residual_layout[gidx(i0)];
+    bool rr = true;
+    for (int l = 1; rr && l < nb; ++l) rr = d->residual_layout[gidx(i0 + l)] == off0 + (int64_t)NR * l;
+    if (rr) {
+      R[0] |= kTableRunFlagResiduals;
+      R[1] = off0;
+    }
+    if (!has_layout) continue;
+    bool cst[CSE_MAX_PARAMETER_BLOCKS];
+    int t[CSE_MAX_PARAMETER_BLOCKS];
+    bool uniform = true;
+    for (int j = 0; j < NB; ++j) {
+      cst[j] = pb(i0, j).is_constant != 0;
+      t[j] = pb(i0, j).tangent_size;
+      for (int l = 1; uniform && l < nb; ++l) {
+        const cse_parameter_block& p = pb(i0 + l, j);
+        uniform = (p.is_constant != 0) == cst[j] && (cst[j] || p.tangent_size == t[j]);
+      }
+    }
+    if (!uniform) continue;
+    // Row (j, kk) of lane l: offsets[layout[gidx] + a NR + kk], a = slot j's
+    // position among the active slots.
+    auto row = [&](int l, int a, int kk) {
+      return d->jacobian_per_residual_offsets[d->jacobian_per_residual_layout[gidx(i0 + l)] + (int64_t)a * NR + kk];
+    };
+    int64_t base[CSE_MAX_PARAMETER_BLOCKS] = {0};
+    int64_t r0 = INT64_MAX;
+    int w = 0, a = 0;
+    for (int j = 0; j < NB; ++j) {
+      if (cst[j]) continue;
+      base[j] = row(0, a++, 0);
+      r0 = std::min(r0, base[j]);
+      w += t[j];
+    }
+    bool bsm = true, crs = true;
+    a = 0;
+    for (int j = 0; j < NB; ++j) {
+      if (cst[j]) continue;
+      for (int l = 0; l < nb && (bsm || crs); ++l)
+        for (int kk = 0; kk < NR; ++kk) {
+          const int64_t v = row(l, a, kk);
+          bsm = bsm && v == base[j] + (int64_t)l * NR * t[j] + (int64_t)kk * t[j];
+          crs = crs && v == base[j] + (int64_t)l * NR * w + (int64_t)kk * w;
+        }
+      ++a;
+      const int64_t cj = base[j] - r0;
+      crs = crs && cj >= 0 && cj + t[j] <= w;
+      for (int j2 = 0; j2 < j; ++j2) {
+        if (cst[j2]) continue;
+        const int64_t c2 = base[j2] - r0;
+        crs = crs && (cj + t[j] <= c2 || c2 + t[j2] <= cj);
+      }
+    }
+    R[0] |= (bsm ? kTableRunFlagBsm : 0) | (crs ? kTableRunFlagCrs : 0);
+    for (int j = 0; j < NB; ++j) R[2 + j] = base[j];
+  }
+}
+
+// The implicit Schur complement's structure (cse_schur_*): one Snavely
+// group on the fused-gradient path with the BlockSparseMatrix layout, its
+// e blocks (slot 1, points) the leading columns [0, e_cols) and its f blocks
+// (slot 0, cameras) the rest, as ITERATIVE_SCHUR's elimination ordering puts
+// them (iterative_schur_complement_solver.cc:66-80).  The e-block runs are cut
+// into wave chunks of whole runs; longer runs are listed as big.
+void BuildSchurPlan(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* P) {
+  SchurPlan& S = P->schur;
+  S = SchurPlan{};
+  if (!only || d->num_groups != 1) return;
+  const GroupPlan& G = *only;
+  if (!G.fuse_ok || G.policy != kAffinePacked || !SnavelyShaped(G.shape) || !P->has_layout ||
+      d->num_constant_parameters > 0)
+    return;
+  const cse_residual_group& g = d->groups[0];
+  const int32_t* ids = g.parameter_block_ids;
+  const int64_t n = g.num_blocks;
+  int32_t pmin = ids[1], pmax = ids[1], cmin = ids[0], cmax = ids[0];
+  for (int64_t i = 0; i < n; ++i) {
+    pmin = std::min(pmin, ids[2 * i + 1]);
+    pmax = std::max(pmax, ids[2 * i + 1]);
+    cmin = std::min(cmin, ids[2 * i]);
+    cmax = std::max(cmax, ids[2 * i]);
+  }
+  const int64_t e_lo = G.delta_base[1] + 3LL * pmin, e_hi = G.delta_base[1] + 3LL * pmax + 3;
+  const int64_t f_lo = G.delta_base[0] + 9LL * cmin, f_hi = G.delta_base[0] + 9LL * cmax + 9;
+  if (e_lo < 0 || f_lo != e_hi || f_hi != d->num_effective_parameters || e_lo != 0) return;
+  S.e_cols = e_hi;
+  S.f_cols = f_hi - f_lo;
+  S.f_col_base = G.delta_base[0] - S.e_cols;
+  // One pass over the runs of equal e block: small runs are packed into
+  // chunks of at most a wave ([begin, end) pairs; chunks never straddle a
+  // big run), big runs listed on their own.
+  std::vector<int64_t>& ranges = P->schur_chunk_begin;
+  std::vector<int64_t>& big = P->schur_big;
+  std::vector<int32_t> cams;
+  bool dup = false;
+  int64_t run_start = 0, chunk_lo = 0;
+  for (int64_t i = 1; i <= n; ++i) {
+    if (i < n && ids[2 * i + 1] == ids[2 * (i - 1) + 1]) continue;
+    const int64_t len = i - run_start;  // the run [run_start, i)
+    cams.assign(len, 0);
+    for (int64_t q = 0; q < len; ++q) cams[q] = ids[2 * (run_start + q)];
+    std::sort(cams.begin(), cams.end());
+    dup = dup || std::adjacent_find(cams.begin(), cams.end()) != cams.end();
+    if (len > kWave) {
+      if (run_start > chunk_lo) ranges.insert(ranges.end(), {chunk_lo, run_start});
+      big.insert(big.end(), {run_start, i});
+      chunk_lo = i;
+    } else if (i - chunk_lo > kWave) {
+      ranges.insert(ranges.end(), {chunk_lo, run_start});
+      chunk_lo = run_start;
+    }
+    run_start = i;
+  }
+  if (n > chunk_lo) ranges.insert(ranges.end(), {chunk_lo, n});
+  S.duplicates = dup;
+  S.nchunks = (int64_t)ranges.size() / 2;
+  S.nbig = (int64_t)big.size() / 2;
+  S.eligible = true;
+}
+
+}  // namespace
+
+void PlanGroup(const cse_problem_desc* d, const cse_options& opts, int gi, ProgramPlan* P,
+               GroupPlan* Gp, GroupTables* T) {
+  const cse_residual_group& g = d->groups[gi];
+  *Gp = GroupPlan{};
+  *T = GroupTables{};
+  GroupPlan& G = *Gp;
+  G.kind = g.functor_kind;
+  G.user = P->users[gi];
+  G.shape = P->shapes[gi];
+  G.loss = g.loss;
+  G.n = g.num_blocks;
+  G.first = g.first_residual_block;
+  const KindShape& k = G.shape;  // follows G.shape when the kind changes below
+
+  // ---- The policy, decided here and nowhere else.
+  G.policy = opts.force_general_layout ? kTable : DetectAffine(d, g, k, &G, T);
+  // Constant slot-0 blocks need the repacked table (their values come from
+  // the constant state through it).
+  if (G.policy != kTable && G.const0 && G.slot0_count > (1 << 20)) G.policy = kTable;
+  // The Jet form of the Snavely functor (cse_options.jacobian_form) is
+  // instantiated for the affine kernels with the LDS-DMA gather and without
+  // held cameras, and for the table kernel: other Snavely groups take the
+  // table path.
+  G.jet = opts.jacobian_form == CSE_JACOBIAN_JET && g.functor_kind == CSE_FUNCTOR_SNAVELY_2_9_3;
+  if (G.jet && G.policy != kTable &&
+      (G.const0 || G.slot0_count <= 0 || G.slot0_count > (1 << 20)))
+    G.policy = kTable;
+  G.affine = G.policy != kTable;
+  if (!G.affine) {
+    G.const0 = false;  // DetectAffine may have set it before giving up
+    T->fbase.clear();
+  }
+  if (G.affine && g.functor_kind == CSE_FUNCTOR_SNAVELY_QUATERNION_2_10_3 &&
+      G.slot0_manifold == CSE_MANIFOLD_QUATERNION_EUCLIDEAN) {
+    // Slot 0 on the quaternion manifold (DetectAffine checked every active
+    // block; a held camera's own manifold is irrelevant): the kernel kind
+    // with the tangent Jacobian (k follows G.shape).
+    G.kind = kKindQuaternionTangent;
+    ShapeOf(G.kind, nullptr, &G.shape);
+  }
+  // Table-path tables: also for const0 groups (their J products use the
+  // table kernels).
+  if (G.const0 || !G.affine) P->any_general = true;
+
+  // ---- Workgroups; every kernel writes one cost partial per wave.
+  if (G.affine) {
+    const int64_t chunks = (g.num_blocks + kWave - 1) / kWave;
+    G.num_wg = std::max<int64_t>(1, (chunks + kWavesPerBlock - 1) / kWavesPerBlock);
+  } else {
+    G.num_wg = (g.num_blocks + kBlockThreads - 1) / kBlockThreads;
+  }
+  G.partial_offset = P->total_wg;
+  P->total_wg += G.num_wg * kWavesPerBlock;
+
+  // The LDS-DMA gather reads slot 0 from a repacked copy refreshed every
+  // evaluation; worth it while the slot-0 id range is small (BAL: the
+  // cameras), otherwise gather 8-byte pieces from the state directly.
+  G.repack0 = G.affine && G.slot0_count > 0 && G.slot0_count <= (1 << 20);
+  if (G.const0) {
+    BuildConst0Tables(d, G, T);
+    if (!T->fbase.empty()) G.fbase0 = T->fbase[0];
+  }
+  const bool fused_kind = FusedKind(G.kind) || UserFused(G.user, k);
+  if (G.affine && P->has_layout) {
+    const int sizes[2] = {k.s0, k.s1};
+    for (int j = 0; j < k.nb; ++j)
+      if (GradSupported(k.nr, sizes[j], G.user, j))
+        BuildGradPlan(g, k, j, &T->grad_info[j], &T->grad[j],
+                      j == 0 && G.const0 ? d->parameter_blocks : nullptr,
+                      j == 0 && k.nb == 2 && fused_kind ? CamGradPasses(g, k) : 1);
+  }
+  BuildTableRuns(d, g, G, P->has_layout, &T->runs);
+  DetectPlain0(d, g, &G);
+
+  // Fused gradient eligibility: a Snavely group on the affine LDS-DMA path
+  // whose slot-1 blocks are sorted (identity plan) and used by no other
+  // group or slot (the fused kernel stores their rows, it does not add),
+  // and whose slot-0 blocks have a chunked plan.
+  const GradPlanInfo* I = T->grad_info;
+  bool ok = fused_kind && G.affine && G.n > 0 && G.repack0 && I[0].ready && !I[0].sorted &&
+            I[0].nchunks > 0 && I[1].ready && I[1].sorted;
+  for (int64_t i = 0; ok && i < g.num_blocks; ++i)
+    ok = P->owner[g.parameter_block_ids[2 * i + 1]] == 2 * gi + 1;
+  G.fuse_ok = ok;
+  G.grad_exact = ok && d->num_groups == 1 && !G.const0 && d->num_constant_parameters == 0 &&
+                 k.s1 == 3 && I[0].all_present && I[1].all_present &&
+                 k.s0 * I[0].count + 3 * I[1].count == d->num_effective_parameters;
+}
+
+void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* P) {
+  // Plus runs: active blocks sorted by state offset, merged while
+  // contiguous with a constant delta shift.
+  std::vector<std::pair<int64_t, int64_t>> blocks;  // (state_offset, index)
+  for (int64_t b = 0; b < d->num_parameter_blocks; ++b) {
+    const cse_parameter_block& pb = d->parameter_blocks[b];
+    if (pb.is_constant) continue;
+    if (pb.manifold == CSE_MANIFOLD_QUATERNION_EUCLIDEAN) {
+      P->plus_quat.push_back({pb.state_offset, pb.delta_offset, pb.size, 0});
+      continue;
+    }
+    if (pb.plus_jacobian_offset >= 0 || pb.tangent_size != pb.size) P->plus_supported = false;
+    blocks.emplace_back(pb.state_offset, b);
+  }
+  std::sort(blocks.begin(), blocks.end());
+  for (const auto& e : blocks) {
+    const cse_parameter_block& pb = d->parameter_blocks[e.second];
+    const int64_t shift = pb.state_offset - pb.delta_offset;
+    auto& R = P->plus_runs;
+    if (!R.empty() && R.back().state_begin + R.back().length == pb.state_offset &&
+        R.back().delta_shift == shift)
+      R.back().length += pb.size;
+    else
+      R.push_back({pb.state_offset, pb.size, shift});
+  }
+  BuildSchurPlan(d, only, P);
+  if (P->any_general) {
+    P->pbs.resize((size_t)d->num_parameter_blocks);
+    for (int64_t b = 0; b < d->num_parameter_blocks; ++b) {
+      const cse_parameter_block& pb = d->parameter_blocks[b];
+      const int64_t pj = pb.manifold == CSE_MANIFOLD_QUATERNION_EUCLIDEAN ? kPlusJacobianQuaternion
+                                                                          : pb.plus_jacobian_offset;
+      P->pbs[b] = {pb.state_offset, pb.delta_offset, pj, pb.tangent_size, pb.is_constant};
+    }
+  }
+}
+
+}  // namespace cse

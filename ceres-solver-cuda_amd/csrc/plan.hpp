@@ -1,0 +1,251 @@
+// plan.hpp -- the host-only planner behind cse_create.
+//
+// Everything the evaluator decides about a cse_problem_desc before it touches
+// the GPU: descriptor validation, the layout policy of each residual group,
+// its gradient plans and store runs, and the program-level tables (Plus runs,
+// the Schur structure, the PbDev table).  Plain C++17 over include/cse.h and
+// host_shared.hpp, so a CPU program (tests/cpp/asan_driver.cpp, built by g++)
+// can drive it under ASan/UBSan.  The library's own plan.o is built by ROCm's
+// clang++, not g++: cse_create's loops over every residual block ran about
+// 15 % slower as g++ -O3 compiled them (the Makefile has the figures).
+//
+// cse_create (cse_evaluator.hip) is the one caller that uploads:
+//   Validate, ValidateGroups                    refuse or accept the descriptor
+//   for each group: PlanGroup, upload, release  one group's tables at a time
+//   PlanProgram, upload
+// The scalars of a plan are plain structs that the evaluator's Group and
+// Group::GradPlan derive from; the tables are std::vectors the caller may
+// drop as soon as they are uploaded (a slot-0 perm is 116 MB at
+// problem-13682).
+#ifndef CSE_PLAN_HPP_
+#define CSE_PLAN_HPP_
+
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/cse.h"
+#include "host_shared.hpp"
+
+// Records msg as the thread's last error (cse_last_error) and returns code.
+int CseFail(int code, const std::string& msg);
+
+namespace cse {
+
+// Layout policy of a group: 0 = table, 1 = affine packed cells (BSM),
+// 2 = affine interleaved rows (CRS).
+enum Policy { kTable = 0, kAffinePacked = 1, kAffineCrs = 2 };
+
+// Internal kernel kinds (never in a descriptor): a group whose slot-0
+// blocks carry a manifold the affine kernels build in registers.
+constexpr int kKindQuaternionTangent = -100;  // SNAVELY_QUATERNION_2_10_3, slot 0 on
+                                              // CSE_MANIFOLD_QUATERNION_EUCLIDEAN
+
+struct KindShape {
+  int nr = 0, nb = 0, data = 0;
+  int sz[kMaxSlots] = {};
+  int s0 = 0, s1 = 0;  // sz[0], sz[1] (0 if absent): the two-slot affine path
+  int x0 = 0;          // slot-0 values gathered (ambient; s0 is the Jacobian's columns)
+};
+
+// The shapes of the library's functor kinds; cse_evaluator.hip ties every row
+// to the kind's KindTraits by static_assert.
+struct KindRow {
+  int kind, nr, nb, data, x0;
+  int sz[kMaxSlots];
+};
+constexpr KindRow kKindRows[] = {
+    {kKindQuaternionTangent, 2, 2, 2, 10, {9, 3}},
+    {CSE_FUNCTOR_SNAVELY_2_9_3, 2, 2, 2, 9, {9, 3}},
+    {CSE_FUNCTOR_SNAVELY_NO_DISTORTION_2_7_3, 2, 2, 2, 7, {7, 3}},
+    {CSE_FUNCTOR_SNAVELY_QUATERNION_2_10_3, 2, 2, 2, 10, {10, 3}},
+    {CSE_FUNCTOR_POINT_DISPLACEMENT_3_3, 3, 1, 3, 3, {3}},
+    {CSE_FUNCTOR_TEST_LINEAR_3_2_3_4, 3, 3, 2, 2, {2, 3, 4}},
+    {CSE_FUNCTOR_TEST_LINEAR_3_4_3_2, 3, 3, 2, 4, {4, 3, 2}},
+    {CSE_FUNCTOR_TEST_LINEAR_2_2_3, 2, 2, 2, 2, {2, 3}},
+    {CSE_FUNCTOR_TEST_LINEAR_3_2_4, 3, 2, 2, 2, {2, 4}},
+    {CSE_FUNCTOR_TEST_LINEAR_4_3_4, 4, 2, 2, 3, {3, 4}},
+    {CSE_FUNCTOR_TEST_BILINEAR_1_2_2, 1, 2, 1, 2, {2, 2}},
+    {CSE_FUNCTOR_TEST_TEN_PARAMETER_1_x10, 1, 10, 1, 1, {1, 1, 1, 1, 1, 1, 1, 1, 1, 1}},
+    {CSE_FUNCTOR_TEST_PARTIAL_OUTPUT_2_1, 2, 1, 1, 1, {1}},
+};
+constexpr const KindRow* KindRowOf(int kind) {
+  for (const KindRow& r : kKindRows)
+    if (r.kind == kind) return &r;
+  return nullptr;
+}
+
+// The shape of a library kind, or of a registered user kind (user = its
+// launch table); false for a kind that is neither.
+bool ShapeOf(int kind, const cse_functor_ops* user, KindShape* k);
+
+// Known-answer-test kinds: general path and trivial loss only.
+inline bool IsTestKind(int kind) { return kind >= 100 && kind < CSE_FUNCTOR_USER_FIRST; }
+
+// Kinds with the fused gradient: the Snavely camera and the quaternion
+// camera on its manifold (the same 2 x (9 + 3) Jacobian shape).
+inline bool FusedKind(int kind) {
+  return kind == CSE_FUNCTOR_SNAVELY_2_9_3 || kind == kKindQuaternionTangent;
+}
+
+// The Jacobian operators built for the Snavely shape (CgnrMultiplyKernel,
+// the Schur kernels) read only the Jacobian's values, so they serve every
+// fused-gradient group of that shape -- 2 residuals, blocks of 9 (tangent)
+// and 3 -- the library's kinds and user kinds alike.
+inline bool SnavelyShaped(const KindShape& k) {
+  return k.nb == 2 && k.nr == 2 && k.s0 == 9 && k.s1 == 3;
+}
+
+// Every affine kernel of a user kind present (the header builds all eight
+// or none).
+bool UserAffine(const cse_functor_ops* u);
+
+// User kinds that registered the fused gradient's launches (cse_functor_ops
+// ABI 5: two slots, slot 1 of 3 parameters): gradient_mode 0's form only
+// (points kernel, CameraGradientKernel, the tail); the other modes, the Jet
+// form and the operators stay with the library's kinds.
+bool UserFused(const cse_functor_ops* user, const KindShape& k);
+
+// A registered user kind and its name; null for any other kind.  The
+// registry lives in cse_evaluator.hip; a caller without user kinds passes a
+// null lookup.
+using UserLookup = const cse_functor_ops* (*)(int kind, std::string* name);
+
+// ---- Gradient post-pass plan of one slot (affine groups with a Jacobian
+// layout): the scalars, and the tables BuildGradPlan fills.
+struct GradPlanInfo {
+  bool ready = false;
+  bool sorted = true;  // blocks already in parameter-block order: no perm, no chunks
+  bool wave = false;   // one wave (not one lane) per parameter block
+  int32_t lo = 0;
+  int64_t count = 0;
+  int passes = 1;
+  int64_t nchunks = 0;
+  int64_t nperm = 0;  // blocks in the plan (all but those with a constant block)
+  bool all_present = false;  // every id in [lo, lo + count) has a block
+};
+struct GradTables {
+  std::vector<int32_t> perm;  // empty = identity
+  std::vector<int64_t> off;
+  // !sorted: chunks of at most kGradChunk blocks
+  std::vector<int64_t> chunk_begin, chunk_off;
+  std::vector<int32_t> chunk_pb;     // parameter block (id) of each chunk
+  std::vector<int32_t> chunk_order;  // passes > 1: the chunks pass-major
+};
+
+int CamGradPasses(const cse_residual_group& g, const KindShape& k);
+void BuildGradPlan(const cse_residual_group& g, const KindShape& k, int j, GradPlanInfo* plan,
+                   GradTables* tables, const cse_parameter_block* cpb = nullptr, int passes = 1);
+
+// ---- One residual group: every decision PlanGroup makes, as scalars.
+struct GroupPlan {
+  int kind = 0;
+  const cse_functor_ops* user = nullptr;  // a registered user functor kind
+  KindShape shape{};
+  cse_loss loss{};
+  int64_t n = 0;
+  bool affine = false;
+  int policy = 0;
+  int64_t partial_offset = 0;
+  int64_t num_wg = 0;
+  int64_t first = 0;
+  // affine parameters
+  int64_t state_base[2] = {0, 0};
+  int64_t delta_base[2] = {0, 0};
+  int64_t res_base = 0;
+  int64_t jac_base[2][3] = {{0, 0, 0}, {0, 0, 0}};
+  int64_t jac_stride[2] = {0, 0};
+  // Repacked slot-0 table (affine path and plain table groups, small id
+  // ranges): repack0 says the evaluator keeps one, slot0_count rows of
+  // packed_stride doubles.
+  bool repack0 = false;
+  int32_t slot0_lo = 0;
+  int64_t slot0_count = 0;
+  int slot0_stride = 0;
+  int packed_stride = 0;  // row stride of the repacked slot-0 table (doubles)
+  // The manifold DetectAffine chose for slot 0, taken from the first block
+  // with an active slot 0 (held blocks carry no Jacobian columns, so their
+  // own manifold does not matter).
+  int slot0_manifold = CSE_MANIFOLD_MATRIX;
+  // Gradient mode 0 writes every gradient row exactly once (grad_exact): one
+  // group, no constant blocks, every camera and point id of its ranges
+  // present and their rows tiling the effective parameters.  Then the tail
+  // kernels assign instead of adding and the gradient is not zeroed first.
+  bool grad_exact = false;
+  // Constant slot-0 blocks on the affine path: GroupTables' bits, src, dlt,
+  // fbase and prev_seg; fbase0 = fbase[0] (HeldWindowsAligned).
+  bool const0 = false;
+  int64_t fbase0 = 0;
+  // Fused gradient (cse::FusedGrad) eligibility.
+  bool fuse_ok = false;
+  // cse_options.jacobian_form = CSE_JACOBIAN_JET on a Snavely group: its
+  // Jacobian kernels are the Jet<double, 12> instantiations (jet_kernels.h).
+  bool jet = false;
+  // Table policy: slot 0 plain in every block (DetectPlain0).
+  bool plain0 = false;
+  int64_t plain0_state_base = 0, plain0_delta_base = 0;
+};
+
+struct GroupTables {
+  // const0: the active-bit table over the slot-0 id range, each id's repack
+  // source (state offset, or -1 - constant-state offset) and delta offset,
+  // per 64-block chunk the offset of its first F cell (BSM) or row block
+  // (CRS) and then the end, and the previous chunk with a non-empty segment.
+  std::vector<uint32_t> bits;
+  std::vector<int64_t> src, dlt, fbase;
+  std::vector<int32_t> prev_seg;
+  // Table policy: each 64-block chunk's store runs, [chunks][2 + nb].
+  std::vector<int64_t> runs;
+  GradPlanInfo grad_info[2];
+  GradTables grad[2];
+};
+
+// ---- The program: what validation counts, what the groups add up to, and
+// the program-level tables.
+struct SchurPlan {
+  bool eligible = false;
+  bool duplicates = false;  // an e block sees one f block twice
+  int64_t e_cols = 0, f_cols = 0;
+  int64_t f_col_base = 0;  // f index of camera id = f_col_base + 9 id
+  int64_t nchunks = 0, nbig = 0;
+};
+
+struct ProgramPlan {
+  // ValidateGroups
+  bool has_layout = false;
+  std::vector<KindShape> shapes;               // per group
+  std::vector<const cse_functor_ops*> users;   // per group, null for a library kind
+  std::vector<std::string> user_names;
+  std::vector<int32_t> owner;  // which (group, slot) uses each parameter block:
+                               // 2 group + slot, -1 none, -2 several
+  bool res_covered = true, jac_covered = true;  // every value is written by some block
+  int64_t bytes_jac = 0, bytes_res = 0;
+  // PlanGroup, summed over the groups
+  int64_t total_wg = 0;
+  bool any_general = false;
+  // PlanProgram
+  bool plus_supported = true;
+  std::vector<PlusRun> plus_runs;
+  std::vector<QuatPlusBlock> plus_quat;
+  SchurPlan schur;
+  std::vector<int64_t> schur_chunk_begin, schur_big;  // [begin, end) pairs
+  std::vector<PbDev> pbs;                             // only when any_general
+};
+
+// The descriptor's own fields and parameter blocks.
+int Validate(const cse_problem_desc* d);
+// Every group and every residual block of it; fills the ValidateGroups part
+// of the plan.  Nothing below may be called on a descriptor these two refuse.
+int ValidateGroups(const cse_problem_desc* d, UserLookup lookup, ProgramPlan* P);
+
+// Plans group gi: G and T are overwritten, P's sums advance.
+void PlanGroup(const cse_problem_desc* d, const cse_options& opts, int gi, ProgramPlan* P,
+               GroupPlan* G, GroupTables* T);
+// After every group: the Plus runs, the PbDev table and the Schur structure
+// (only = the plan of the program's one group, null when it has several).
+void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* P);
+
+}  // namespace cse
+
+#endif  // CSE_PLAN_HPP_

@@ -1,25 +1,30 @@
 // ASan/UBSan driver for the host code (SURVEY.md §5 "Race detection /
 // sanitizers"; the reference's SANITIZERS option, CMakeLists.txt:156-158):
-// the layout builders (ceres-solver-cuda_amd/csrc/layout.cpp), the CPU oracle
-// (oracle/oracle.cpp) and -- built with CSE_ASAN_HIP -- the host half of
-// libcse (cse_evaluator.hip, multi_device.hip: descriptor validation, layout
-// detection, plans, the multi-device sharding, the error paths), all
-// instrumented.  Device code is not instrumented (GPU sanitizers are not
-// available on this pool).
+// the layout builders (ceres-solver-cuda_amd/csrc/layout.cpp), the host-only
+// planner behind cse_create (csrc/plan.cpp: descriptor validation, layout
+// detection, gradient and Schur plans, table runs), the CPU oracle
+// (oracle/oracle.cpp) and -- built with CSE_ASAN_HIP -- the rest of the host
+// half of libcse (cse_evaluator.hip, multi_device.hip: uploads, the
+// multi-device sharding, the error paths), all instrumented.  Device code is
+// not instrumented (GPU sanitizers are not available on this pool).
 //
 // Part A (CPU): a synthetic BAL-shaped problem; the layout builders' offsets
 // must equal the oracle's writers (block_jacobian_writer.cc /
 // compressed_row_jacobian_writer.cc restatements), and the oracle evaluates
-// both formats on 1 and 3 threads (bit-identical).
+// both formats on 1 and 3 threads (bit-identical).  Then the planner on the
+// descriptor part B creates evaluators from (CheckPlanner): every expectation
+// is worked out from the descriptor by brute force.
 // Part B (CSE_ASAN_HIP, needs a GPU): cse_create / cse_evaluate and
 // cse_create_multi over {0, 0, 0} against the oracle (the reference's
 // isApprox 1e-13), plus malformed descriptors.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
+#include "../../ceres-solver-cuda_amd/csrc/plan.hpp"
 #include "../../include/cse.h"
 #include "../../oracle/oracle.h"
 
@@ -93,11 +98,18 @@ struct Layout {
   int64_t num_values = 0;
 };
 
-static Layout BuildLayout(const Bal& b, bool crs) {
+// held >= 0: that camera is constant, its values first in the constant
+// state; the later cameras close the gap in the state and the gradient.
+static Layout BuildLayout(const Bal& b, bool crs, int held = -1) {
   Layout L;
   for (int p = 0; p < b.P; ++p) L.pbs.push_back({3, 3, 0, 0, 3LL * p, 3LL * p, -1});
-  for (int c = 0; c < b.C; ++c)
-    L.pbs.push_back({9, 9, 0, 0, 3LL * b.P + 9LL * c, 3LL * b.P + 9LL * c, -1});
+  for (int c = 0; c < b.C; ++c) {
+    const int64_t at = 3LL * b.P + 9LL * (c - (held >= 0 && c > held ? 1 : 0));
+    if (c == held) L.pbs.push_back({9, 9, 1, 0, 0, 0, -1});
+    else L.pbs.push_back({9, 9, 0, 0, at, at, -1});
+  }
+  int64_t held_blocks = 0;
+  for (int64_t i = 0; i < b.O; ++i) held_blocks += b.cam[i] == held;
   L.begin.push_back(0);
   for (int64_t i = 0; i < b.O; ++i) {
     L.params.push_back(b.P + b.cam[i]);
@@ -108,7 +120,7 @@ static Layout BuildLayout(const Bal& b, bool crs) {
   const int64_t npb = (int64_t)L.pbs.size();
   const int64_t count = cse_layout_offsets_count(npb, L.pbs.data(), b.O, L.begin.data(),
                                                  L.params.data(), L.nres.data());
-  EXPECT(count == 4 * b.O);
+  EXPECT(count == 4 * b.O - 2 * held_blocks);
   L.res_layout.resize(b.O);
   L.jac_layout.resize(b.O);
   L.jac_offsets.resize(count);
@@ -128,8 +140,415 @@ static Layout BuildLayout(const Bal& b, bool crs) {
                                      L.jac_offsets.data(), &L.num_values, rows.data(),
                                      cols.data()) == CSE_OK);
   }
-  EXPECT(L.num_values == 24 * b.O);
+  EXPECT(L.num_values == 24 * b.O - 18 * held_blocks);
   return L;
+}
+
+// The descriptor of the problem: one Snavely group with the Huber loss, as
+// cse_create gets it in part B.  Points into b and L.
+struct Desc {
+  cse_residual_group g{};
+  std::vector<int32_t> ids;
+  cse_problem_desc d{};
+};
+
+static void MakeDesc(const Bal& b, const Layout& L, Desc* D) {
+  cse_residual_group& g = D->g;
+  g.functor_kind = CSE_FUNCTOR_SNAVELY_2_9_3;
+  g.loss = cse_loss{CSE_LOSS_HUBER, 0, 1.0, 1.0, {}};
+  g.num_blocks = b.O;
+  D->ids.resize(2 * b.O);
+  for (int64_t i = 0; i < b.O; ++i) {
+    D->ids[2 * i] = b.P + b.cam[i];
+    D->ids[2 * i + 1] = b.pt[i];
+  }
+  g.parameter_block_ids = D->ids.data();
+  g.functor_data = b.obs.data();
+  cse_problem_desc& d = D->d;
+  d.abi_version = CSE_ABI_VERSION;
+  d.num_groups = 1;
+  d.groups = &D->g;
+  d.num_parameter_blocks = (int64_t)L.pbs.size();
+  d.parameter_blocks = L.pbs.data();
+  for (const cse_parameter_block& pb : L.pbs) {
+    (pb.is_constant ? d.num_constant_parameters : d.num_parameters) += pb.size;
+    if (!pb.is_constant) d.num_effective_parameters += pb.tangent_size;
+  }
+  d.num_residual_blocks = b.O;
+  d.num_residuals = 2 * b.O;
+  d.residual_layout = L.res_layout.data();
+  d.jacobian_per_residual_layout = L.jac_layout.data();
+  d.jacobian_per_residual_offsets = L.jac_offsets.data();
+  d.num_jacobian_per_residual_offsets = (int64_t)L.jac_offsets.size();
+  d.num_jacobian_values = L.num_values;
+}
+
+// cse_default_options' values (that function is in the HIP half).
+static cse_options DefaultOptions() {
+  cse_options o{};
+  o.device = -1;
+  o.check_finite = 1;
+  o.apply_loss_function = 1;
+  return o;
+}
+
+// cse_create's planning steps without its uploads (plan.hpp).
+struct Planned {
+  cse::ProgramPlan P;
+  cse::GroupPlan G;
+  cse::GroupTables T;
+  bool planned = false;
+};
+
+static int Plan(const cse_problem_desc& d, const cse_options& o, Planned* out) {
+  int rc = cse::Validate(&d);
+  if (rc) return rc;
+  if ((rc = cse::ValidateGroups(&d, nullptr, &out->P))) return rc;
+  cse::PlanGroup(&d, o, 0, &out->P, &out->G, &out->T);
+  cse::PlanProgram(&d, &out->G, &out->P);
+  out->planned = true;
+  return CSE_OK;
+}
+
+// A gradient plan of slot j against the ids: perm is a permutation of the
+// blocks whose slot-j parameter block is active, ordered by (parameter
+// block, pass, block); off counts them per parameter block; the chunks tile
+// the order, each within one parameter block and one pass and no longer than
+// kGradChunk; chunk_order lists every chunk once, pass-major.
+static void CheckGradPlan(const cse_problem_desc& d, int j, int passes, const cse::GradPlanInfo& I,
+                          const cse::GradTables& T) {
+  const cse_residual_group& g = d.groups[0];
+  const int64_t n = g.num_blocks;
+  auto id_of = [&](int64_t i) { return g.parameter_block_ids[2 * i + j]; };
+  auto pass_of = [&](int64_t i) { return (int64_t)(i * passes / n); };
+  int32_t lo = INT32_MAX, hi = INT32_MIN;
+  std::vector<int64_t> kept;
+  for (int64_t i = 0; i < n; ++i) {
+    lo = std::min(lo, id_of(i));
+    hi = std::max(hi, id_of(i));
+    if (!d.parameter_blocks[id_of(i)].is_constant) kept.push_back(i);
+  }
+  EXPECT(I.ready && I.lo == lo && I.count == (int64_t)hi - lo + 1 && I.nperm == (int64_t)kept.size());
+  // off: the running count per parameter block.
+  EXPECT((int64_t)T.off.size() == I.count + 1);
+  if ((int64_t)T.off.size() != I.count + 1) return;
+  int64_t running = 0;
+  bool all_present = true;
+  for (int64_t p = 0; p < I.count; ++p) {
+    EXPECT(T.off[p] == running);
+    int64_t here = 0;
+    for (int64_t i : kept) here += id_of(i) == lo + p;
+    all_present = all_present && here > 0;
+    running += here;
+  }
+  EXPECT(T.off[I.count] == running && running == (int64_t)kept.size());
+  EXPECT(I.all_present == all_present);
+  if (I.sorted) {  // identity: the kept blocks are all of them, already in order
+    EXPECT(T.perm.empty() && T.chunk_begin.empty() && I.nchunks == 0);
+    EXPECT((int64_t)kept.size() == n);
+    for (int64_t i = 1; i < n; ++i) EXPECT(id_of(i - 1) <= id_of(i));
+    return;
+  }
+  EXPECT(T.perm.size() == kept.size());
+  if (T.perm.size() != kept.size()) return;
+  std::vector<char> seen(n, 0);
+  for (size_t q = 0; q < T.perm.size(); ++q) {
+    const int64_t i = T.perm[q];
+    EXPECT(i >= 0 && i < n);
+    if (i < 0 || i >= n) return;
+    EXPECT(!seen[i] && !d.parameter_blocks[id_of(i)].is_constant);
+    seen[i] = 1;
+    if (q > 0) {
+      const int64_t h = T.perm[q - 1];
+      const bool ordered = id_of(h) != id_of(i)       ? id_of(h) < id_of(i)
+                           : pass_of(h) != pass_of(i) ? pass_of(h) < pass_of(i)
+                                                      : h < i;
+      EXPECT(ordered);
+    }
+  }
+  // Chunks.
+  const int64_t nc = I.nchunks;
+  EXPECT(nc > 0 && (int64_t)T.chunk_begin.size() == nc + 1 && (int64_t)T.chunk_pb.size() == nc &&
+         (int64_t)T.chunk_off.size() == I.count + 1 && I.passes == passes);
+  if ((int64_t)T.chunk_begin.size() != nc + 1 || (int64_t)T.chunk_pb.size() != nc ||
+      (int64_t)T.chunk_off.size() != I.count + 1)
+    return;
+  EXPECT(T.chunk_begin[0] == 0 && T.chunk_begin[nc] == (int64_t)kept.size());
+  std::vector<int64_t> chunk_pass(nc, 0);
+  for (int64_t c = 0; c < nc; ++c) {
+    const int64_t q0 = T.chunk_begin[c], q1 = T.chunk_begin[c + 1];
+    EXPECT(q0 < q1 && q1 - q0 <= cse::kGradChunk && q1 <= (int64_t)kept.size());
+    if (!(q0 < q1 && q1 <= (int64_t)kept.size())) return;
+    chunk_pass[c] = pass_of(T.perm[q0]);
+    for (int64_t q = q0; q < q1; ++q)
+      EXPECT(id_of(T.perm[q]) == T.chunk_pb[c] && pass_of(T.perm[q]) == chunk_pass[c]);
+  }
+  for (int64_t p = 0; p <= I.count; ++p) {  // chunk_off[p]: the first chunk at or after block p
+    int64_t first = 0;
+    while (first < nc && T.chunk_pb[first] < lo + p) ++first;
+    EXPECT(T.chunk_off[p] == first);
+  }
+  if (passes > 1) {
+    EXPECT((int64_t)T.chunk_order.size() == nc);
+    std::vector<char> listed(nc, 0);
+    for (size_t q = 0; q < T.chunk_order.size(); ++q) {
+      const int32_t c = T.chunk_order[q];
+      EXPECT(c >= 0 && c < nc);
+      if (c < 0 || c >= nc) return;
+      EXPECT(!listed[c]);
+      listed[c] = 1;
+      if (q > 0) {
+        const int32_t h = T.chunk_order[q - 1];
+        EXPECT(chunk_pass[h] < chunk_pass[c] || (chunk_pass[h] == chunk_pass[c] && h < c));
+      }
+    }
+  } else {
+    EXPECT(T.chunk_order.empty());
+  }
+}
+
+// The slot-0 id range of the group: exactly the cameras.
+static void CheckCameraRange(const Bal& b, const cse::GroupPlan& G) {
+  int lo = b.C, hi = -1;
+  for (int64_t i = 0; i < b.O; ++i) {
+    lo = std::min(lo, b.cam[i]);
+    hi = std::max(hi, b.cam[i]);
+  }
+  EXPECT(lo == 0 && hi == b.C - 1);  // this generator uses every camera
+  EXPECT(G.repack0 && G.slot0_lo == b.P + lo && G.slot0_count == hi - lo + 1 && G.slot0_count == 9);
+  EXPECT(G.packed_stride == 16);
+}
+
+static void CheckSchurPlan(const Bal& b, const cse::ProgramPlan& P) {
+  const cse::SchurPlan& S = P.schur;
+  EXPECT(S.eligible && S.e_cols == 3 * b.P && S.f_cols == 9 * b.C);
+  EXPECT((int64_t)P.schur_chunk_begin.size() == 2 * S.nchunks && (int64_t)P.schur_big.size() == 2 * S.nbig);
+  auto boundary = [&](int64_t i) { return i == 0 || i == b.O || b.pt[i] != b.pt[i - 1]; };
+  // (begin, end, big) of both lists in order: together they tile [0, n).
+  struct Range { int64_t lo, hi; bool big; };
+  std::vector<Range> ranges;
+  for (size_t q = 0; q + 1 < P.schur_chunk_begin.size(); q += 2)
+    ranges.push_back({P.schur_chunk_begin[q], P.schur_chunk_begin[q + 1], false});
+  for (size_t q = 0; q + 1 < P.schur_big.size(); q += 2)
+    ranges.push_back({P.schur_big[q], P.schur_big[q + 1], true});
+  std::sort(ranges.begin(), ranges.end(), [](const Range& x, const Range& y) { return x.lo < y.lo; });
+  int64_t at = 0;
+  for (const Range& r : ranges) {
+    EXPECT(r.lo == at && r.hi > r.lo && r.hi <= b.O);
+    if (!(r.lo == at && r.hi > r.lo && r.hi <= b.O)) return;
+    EXPECT(boundary(r.lo) && boundary(r.hi));
+    if (r.big) {  // one run, longer than a wave
+      EXPECT(r.hi - r.lo > cse::kWave);
+      for (int64_t i = r.lo + 1; i < r.hi; ++i) EXPECT(!boundary(i));
+    } else {
+      EXPECT(r.hi - r.lo <= cse::kWave);
+    }
+    at = r.hi;
+  }
+  EXPECT(at == b.O);
+  bool dup = false;
+  for (int64_t i = 0; i < b.O; ++i)
+    for (int64_t h = i + 1; h < b.O && b.pt[h] == b.pt[i]; ++h) dup = dup || b.cam[h] == b.cam[i];
+  EXPECT(S.duplicates == dup);
+}
+
+// force_general_layout: the table policy, slot 0 plain, and every chunk's
+// store run record.
+static void CheckTableRuns(const Bal& b, const Layout& L, bool crs, const Planned& pl) {
+  EXPECT(pl.G.policy == cse::kTable && !pl.G.affine && !pl.G.const0 && pl.G.plain0);
+  CheckCameraRange(b, pl.G);
+  EXPECT(pl.G.plain0_state_base == 3LL * b.P - 9LL * b.P && pl.G.plain0_delta_base == pl.G.plain0_state_base);
+  const int64_t nch = (b.O + cse::kWave - 1) / cse::kWave, W = 4;
+  EXPECT(nch == 25 && b.O % cse::kWave == 61);
+  EXPECT((int64_t)pl.T.runs.size() == nch * W);
+  if ((int64_t)pl.T.runs.size() != nch * W) return;
+  for (int64_t c = 0; c < nch; ++c) {
+    const int64_t* R = &pl.T.runs[c * W];
+    const int64_t i0 = c * cse::kWave;
+    EXPECT((R[0] & cse::kTableRunFlagResiduals) != 0 && R[1] == L.res_layout[i0]);
+    EXPECT(((R[0] & cse::kTableRunFlagBsm) != 0) == !crs);
+    EXPECT(((R[0] & cse::kTableRunFlagCrs) != 0) == crs);
+    EXPECT(R[2] == L.jac_offsets[L.jac_layout[i0]] && R[3] == L.jac_offsets[L.jac_layout[i0] + 2]);
+  }
+}
+
+// One held camera in the middle of the id range.
+static void CheckHeldCamera(const Bal& b, bool crs) {
+  const int held = b.C / 2;
+  const Layout L = BuildLayout(b, crs, held);
+  Desc D;
+  MakeDesc(b, L, &D);
+  const cse_problem_desc& d = D.d;
+  EXPECT(d.num_constant_parameters == 9);
+  const std::vector<double> cstate(b.state.begin() + 3 * b.P + 9 * held, b.state.begin() + 3 * b.P + 9 * held + 9);
+  D.d.constant_state = cstate.data();
+  Planned pl;
+  EXPECT(Plan(d, DefaultOptions(), &pl) == CSE_OK);
+  if (!pl.planned) return;
+  const cse::GroupPlan& G = pl.G;
+  EXPECT(G.affine && G.const0 && G.policy == (crs ? cse::kAffineCrs : cse::kAffinePacked));
+  CheckCameraRange(b, G);
+  EXPECT(pl.P.any_general && !G.grad_exact);
+  // Active bits, repack sources and delta offsets per camera id.
+  EXPECT(pl.T.bits.size() == 1 && pl.T.src.size() == 9 && pl.T.dlt.size() == 9);
+  if (pl.T.bits.size() != 1 || pl.T.src.size() != 9 || pl.T.dlt.size() != 9) return;
+  for (int c = 0; c < b.C; ++c) {
+    const cse_parameter_block& pb = L.pbs[b.P + c];
+    EXPECT(((pl.T.bits[0] >> c) & 1u) == (c != held ? 1u : 0u));
+    EXPECT(pl.T.src[c] == (c == held ? -1 - pb.state_offset : pb.state_offset));
+    EXPECT(pl.T.dlt[c] == (c == held ? -1 : pb.delta_offset));
+  }
+  EXPECT((pl.T.bits[0] >> b.C) == 0);
+  // fbase: per chunk its first F cell (BSM) or row block (CRS), then the end.
+  const int64_t nch = (b.O + cse::kWave - 1) / cse::kWave;
+  EXPECT((int64_t)pl.T.fbase.size() == nch + 1 && (int64_t)pl.T.prev_seg.size() == nch);
+  if ((int64_t)pl.T.fbase.size() != nch + 1 || (int64_t)pl.T.prev_seg.size() != nch) return;
+  for (int64_t c = 0; c < nch; ++c) EXPECT(pl.T.fbase[c] <= pl.T.fbase[c + 1]);
+  int64_t end = 0;
+  std::vector<char> segment(nch, 0);  // does the chunk hold an F cell / a row block?
+  for (int64_t i = 0; i < b.O; ++i) {
+    const bool active = b.cam[i] != held;
+    const int64_t base = L.jac_layout[i];
+    if (crs) {  // every block has rows: the widest end of its last row
+      const int rows = active ? 4 : 2;
+      for (int r = 0; r < rows; ++r)
+        end = std::max(end, L.jac_offsets[base + r] + (active && r < 2 ? 9 : 3));
+      segment[i / cse::kWave] = 1;
+    } else if (active) {
+      end = std::max(end, L.jac_offsets[base + 1] + 9);
+      segment[i / cse::kWave] = 1;
+    }
+  }
+  EXPECT(pl.T.fbase[nch] == end);
+  EXPECT(G.fbase0 == pl.T.fbase[0]);
+  int32_t last = -1;
+  for (int64_t c = 0; c < nch; ++c) {
+    EXPECT(pl.T.prev_seg[c] == last);
+    EXPECT((pl.T.fbase[c + 1] > pl.T.fbase[c]) == (segment[c] != 0));
+    if (segment[c]) last = (int32_t)c;
+  }
+  // The slot-0 plan leaves out exactly the held camera's blocks.
+  int64_t held_blocks = 0;
+  for (int64_t i = 0; i < b.O; ++i) held_blocks += b.cam[i] == held;
+  EXPECT(held_blocks > 0 && pl.T.grad_info[0].nperm == b.O - held_blocks && !pl.T.grad_info[0].all_present);
+  CheckGradPlan(d, 0, 1, pl.T.grad_info[0], pl.T.grad[0]);
+  CheckGradPlan(d, 1, 1, pl.T.grad_info[1], pl.T.grad[1]);
+  EXPECT(pl.T.grad_info[1].sorted);
+}
+
+// The planner on the descriptor of part B, no GPU.
+static void CheckPlanner(const Bal& b, const Layout& L, bool crs, const Desc& D) {
+  const cse_problem_desc& d = D.d;
+  EXPECT(b.O == 1597 && b.O / cse::kWave == 24);
+  {  // Default options.
+    Planned pl;
+    EXPECT(Plan(d, DefaultOptions(), &pl) == CSE_OK);
+    if (!pl.planned) return;
+    const cse::GroupPlan& G = pl.G;
+    EXPECT(G.affine && !G.const0 && !G.plain0 && !G.jet && G.kind == CSE_FUNCTOR_SNAVELY_2_9_3);
+    EXPECT(G.policy == (crs ? cse::kAffineCrs : cse::kAffinePacked));
+    CheckCameraRange(b, G);
+    EXPECT(G.fuse_ok && G.grad_exact);
+    EXPECT(G.n == b.O && G.num_wg == (25 + 3) / 4 && G.partial_offset == 0 && pl.P.total_wg == 4 * G.num_wg);
+    EXPECT(!pl.P.any_general && pl.P.pbs.empty() && pl.P.res_covered && pl.P.jac_covered);
+    EXPECT(pl.P.plus_supported && pl.P.plus_quat.empty() && pl.P.plus_runs.size() == 1);
+    EXPECT(pl.T.grad_info[1].sorted && pl.T.grad[1].perm.empty());  // points: the identity
+    EXPECT(!pl.T.grad_info[0].sorted);
+    CheckGradPlan(d, 0, 1, pl.T.grad_info[0], pl.T.grad[0]);
+    CheckGradPlan(d, 1, 1, pl.T.grad_info[1], pl.T.grad[1]);
+    EXPECT(cse::CamGradPasses(D.g, pl.G.shape) == 1);
+    if (crs) {
+      EXPECT(!pl.P.schur.eligible);
+    } else {
+      CheckSchurPlan(b, pl.P);
+      EXPECT(pl.P.schur.e_cols == 3 * 400 && pl.P.schur.f_cols == 9 * 9);
+      EXPECT(pl.P.schur.duplicates);  // k = 0 and k = 3 map to one camera
+      EXPECT(pl.P.schur.nbig == 0);   // no point has more than 7 observations
+    }
+  }
+  {  // force_general_layout.
+    cse_options o = DefaultOptions();
+    o.force_general_layout = 1;
+    Planned pl;
+    EXPECT(Plan(d, o, &pl) == CSE_OK);
+    if (pl.planned) {
+      CheckTableRuns(b, L, crs, pl);
+      EXPECT(pl.P.any_general && (int64_t)pl.P.pbs.size() == d.num_parameter_blocks);
+      EXPECT(!pl.G.fuse_ok && !pl.P.schur.eligible && !pl.T.grad_info[0].ready);
+    }
+  }
+  CheckHeldCamera(b, crs);
+  {  // Three passes, which CamGradPasses reaches only at a far larger size.
+    cse::KindShape k;
+    EXPECT(cse::ShapeOf(CSE_FUNCTOR_SNAVELY_2_9_3, nullptr, &k));
+    cse::GradPlanInfo I;
+    cse::GradTables T;
+    cse::BuildGradPlan(D.g, k, 0, &I, &T, nullptr, 3);
+    CheckGradPlan(d, 0, 3, I, T);
+  }
+  // Malformed descriptors: CSE_ERR_INVALID, nothing planned.
+  auto refused = [&](const cse_problem_desc& bad) {
+    Planned pl;
+    EXPECT(Plan(bad, DefaultOptions(), &pl) == CSE_ERR_INVALID && !pl.planned);
+  };
+  {
+    cse_problem_desc bad = d;
+    std::vector<int64_t> broken = L.jac_offsets;
+    broken[5] = L.num_values;  // out of range
+    bad.jacobian_per_residual_offsets = broken.data();
+    refused(bad);
+  }
+  {
+    std::vector<int32_t> bad_ids = D.ids;
+    bad_ids[7] = (int32_t)L.pbs.size();
+    cse_residual_group bg = D.g;
+    bg.parameter_block_ids = bad_ids.data();
+    cse_problem_desc bad = d;
+    bad.groups = &bg;
+    refused(bad);
+  }
+  {
+    cse_problem_desc bad = d;
+    std::vector<int64_t> broken = L.res_layout;
+    broken[3] = d.num_residuals - 1;  // its second residual is past the end
+    bad.residual_layout = broken.data();
+    refused(bad);
+  }
+  {
+    cse_problem_desc bad = d;
+    std::vector<cse_parameter_block> pbs = L.pbs;
+    pbs[b.pt[0]].size = 4;  // a point of 4 values in a state that has room for it
+    bad.parameter_blocks = pbs.data();
+    refused(bad);
+  }
+}
+
+// The sizes the problem above does not reach: two cameras of about 2000
+// blocks each (slot-0 chunks cut at kGradChunk) and points of up to 90
+// observations (e-block runs longer than a wave: the Schur plan's big runs).
+static void CheckLongRuns() {
+  const Bal b = MakeBal(2, 100, 90);
+  const Layout L = BuildLayout(b, false);
+  Desc D;
+  MakeDesc(b, L, &D);
+  Planned pl;
+  EXPECT(Plan(D.d, DefaultOptions(), &pl) == CSE_OK);
+  if (!pl.planned) return;
+  EXPECT(pl.G.policy == cse::kAffinePacked && pl.G.fuse_ok && pl.G.slot0_count == 2);
+  CheckGradPlan(D.d, 0, 1, pl.T.grad_info[0], pl.T.grad[0]);
+  CheckGradPlan(D.d, 1, 1, pl.T.grad_info[1], pl.T.grad[1]);
+  int64_t longest = 0;
+  for (int64_t c = 0; c < pl.T.grad_info[0].nchunks; ++c)
+    longest = std::max(longest, pl.T.grad[0].chunk_begin[c + 1] - pl.T.grad[0].chunk_begin[c]);
+  EXPECT(b.O > 4 * cse::kGradChunk && pl.T.grad_info[0].nchunks > 2 && longest == cse::kGradChunk);
+  CheckSchurPlan(b, pl.P);
+  int64_t long_runs = 0, run_start = 0;  // runs of one point longer than a wave
+  for (int64_t i = 1; i <= b.O; ++i)
+    if (i == b.O || b.pt[i] != b.pt[i - 1]) {
+      long_runs += i - run_start > cse::kWave;
+      run_start = i;
+    }
+  EXPECT(long_runs > 0 && pl.P.schur.nbig == long_runs);
 }
 
 struct OracleInputs {
@@ -200,38 +619,22 @@ static void RunFormat(const Bal& b, bool crs) {
   std::printf("%s oracle: cost %.15e, %lld values\n", crs ? "CRS" : "BSM", o1.cost,
               (long long)L.num_values);
 
+  // The descriptor cse_create gets in part B; here the planner alone.
+  Desc D;
+  MakeDesc(b, L, &D);
+  EXPECT(D.d.num_parameters == sz.num_parameters && D.d.num_residuals == sz.num_residuals &&
+         D.d.num_effective_parameters == sz.num_effective_parameters);
+  CheckPlanner(b, L, crs, D);
+
 #ifdef CSE_ASAN_HIP
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
     std::printf("no GPU: part B skipped\n");
     return;
   }
-  cse_residual_group g{};
-  g.functor_kind = CSE_FUNCTOR_SNAVELY_2_9_3;
-  g.loss = cse_loss{CSE_LOSS_HUBER, 0, 1.0, 1.0};
-  g.num_blocks = b.O;
-  std::vector<int32_t> ids(2 * b.O);
-  for (int64_t i = 0; i < b.O; ++i) {
-    ids[2 * i] = b.P + b.cam[i];
-    ids[2 * i + 1] = b.pt[i];
-  }
-  g.parameter_block_ids = ids.data();
-  g.functor_data = b.obs.data();
-  cse_problem_desc d{};
-  d.abi_version = CSE_ABI_VERSION;
-  d.num_groups = 1;
-  d.groups = &g;
-  d.num_parameter_blocks = (int64_t)L.pbs.size();
-  d.parameter_blocks = L.pbs.data();
-  d.num_parameters = sz.num_parameters;
-  d.num_effective_parameters = sz.num_effective_parameters;
-  d.num_residual_blocks = b.O;
-  d.num_residuals = sz.num_residuals;
-  d.residual_layout = L.res_layout.data();
-  d.jacobian_per_residual_layout = L.jac_layout.data();
-  d.jacobian_per_residual_offsets = L.jac_offsets.data();
-  d.num_jacobian_per_residual_offsets = (int64_t)L.jac_offsets.size();
-  d.num_jacobian_values = L.num_values;
+  const cse_residual_group& g = D.g;
+  const std::vector<int32_t>& ids = D.ids;
+  const cse_problem_desc& d = D.d;
   cse_options opts;
   cse_default_options(&opts);
   const int32_t devs[3] = {0, 0, 0};
@@ -323,6 +726,7 @@ int main() {
   const Bal b = MakeBal(9, 400, 7);
   RunFormat(b, false);
   RunFormat(b, true);
+  CheckLongRuns();
   if (failures) {
     std::printf("%d failure(s)\n", failures);
     return Finish(1);

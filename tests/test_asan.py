@@ -1,10 +1,12 @@
 """AddressSanitizer + UBSan runs of the host code (the
 reference's SANITIZERS CMake option, CMakeLists.txt:156-158).
 
-CPU: the layout builders (ceres-solver-cuda_amd/csrc/layout.cpp) and the
-oracle (oracle/oracle.cpp) instrumented, tests/cpp/asan_driver.cpp part A.
-GPU: the host half of libcse (descriptor validation, layout detection,
-gradient and Schur plans, the multi-device sharding, error paths) and the
+CPU: the layout builders (ceres-solver-cuda_amd/csrc/layout.cpp), the
+host-only planner behind cse_create (csrc/plan.cpp: descriptor validation,
+layout detection, gradient and Schur plans, table runs) and the oracle
+(oracle/oracle.cpp) instrumented, tests/cpp/asan_driver.cpp part A.
+GPU: the whole host half of libcse (the planner again, the uploads, the
+multi-device sharding, error paths) and the
 C++ ProblemCUDA facade instrumented, run against the device: asan_driver
 part B and tests/cpp/test_problem_cuda.cpp.  The instrumented binaries are
 built in this container (`make -C tests/cpp asan-hip`, by build()); device
