@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(HERE, "..", "lib", "libcse.so"))
 
-CSE_ABI_VERSION = 5
+CSE_ABI_VERSION = 6
 
 # cse_options.jacobian_form (cse_jacobian_form)
 JACOBIAN_CLOSED_FORM = 0
@@ -90,7 +90,7 @@ class cse_parameter_block(C.Structure):
 
 
 class cse_residual_group(C.Structure):
-    _fields_ = [("functor_kind", C.c_int32), ("reserved", C.c_int32),
+    _fields_ = [("functor_kind", C.c_int32), ("loss_data_size", C.c_int32),
                 ("loss", cse_loss), ("num_blocks", C.c_int64),
                 ("residual_block_index", C.POINTER(C.c_int64)),
                 ("first_residual_block", C.c_int64),

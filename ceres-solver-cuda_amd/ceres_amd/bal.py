@@ -290,7 +290,8 @@ def to_quaternion_cameras(cameras):
 
 
 def program(cameras, points, cam_idx, pt_idx, obs, loss=None, kind=None,
-            format=BLOCK_SPARSE, compile=True, quaternion_manifold=False, constant_cameras=()):
+            format=BLOCK_SPARSE, compile=True, quaternion_manifold=False, constant_cameras=(),
+            loss_data=None):
     """The Schur-ordered Program of a BAL problem (observations must
     already be point-major, as synthetic() returns and
     schur_residual_order() produces).  10-parameter (quaternion) cameras
@@ -299,7 +300,9 @@ def program(cameras, points, cam_idx, pt_idx, obs, loss=None, kind=None,
     bundle_adjuster --use_quaternions --use_manifolds does
     (examples/bundle_adjuster.cc:337-345).  constant_cameras: camera indices
     held constant (Problem::SetParameterBlockConstant, e.g. to fix the gauge):
-    their values move to the constant state and they get no delta columns."""
+    their values move to the constant state and they get no delta columns.
+    loss_data: (observations, 2) per-block loss parameters (a, scale), in the
+    observations' order; `loss` then gives the loss kind and `scaled`."""
     if kind is None:
         kind = _cse.SNAVELY_QUATERNION_2_10_3 if cameras.shape[1] == 10 else _cse.SNAVELY_2_9_3
     C, P = cameras.shape[0], points.shape[0]
@@ -313,6 +316,8 @@ def program(cameras, points, cam_idx, pt_idx, obs, loss=None, kind=None,
     ids[:, 1] = pt_idx
     group = ResidualGroup(kind, loss or Loss.trivial(), ids, np.ascontiguousarray(obs, np.float64),
                           None, 0)
+    if loss_data is not None:
+        group.loss_data = np.ascontiguousarray(np.asarray(loss_data, np.float64).reshape(len(cam_idx), 2))
     const = np.zeros(npb, np.int32)
     cstate = np.zeros(0)
     if len(constant_cameras):
@@ -337,12 +342,18 @@ def program(cameras, points, cam_idx, pt_idx, obs, loss=None, kind=None,
 
 def synthetic_program(name_or_counts, loss=None, format=BLOCK_SPARSE, seed=0xCE2E5,
                       compile=True, quaternion=False, quaternion_manifold=False,
-                      constant_cameras=()):
+                      constant_cameras=(), loss_data=None, kind=None):
     """A synthetic BAL Program; quaternion: 10-parameter cameras
-    (to_quaternion_cameras), optionally on the quaternion manifold."""
+    (to_quaternion_cameras), optionally on the quaternion manifold.
+    loss_data: per-block loss parameters (program()).  kind: another functor
+    kind over the same blocks (SNAVELY_NO_DISTORTION_2_7_3 takes the first 7
+    camera parameters)."""
     counts = CONFIGS[name_or_counts] if isinstance(name_or_counts, str) else name_or_counts
     cams, pts, ci, pi, obs = synthetic(*counts, seed=seed)
     if quaternion or quaternion_manifold:
         cams = to_quaternion_cameras(cams)
-    return program(cams, pts, ci, pi, obs, loss=loss, format=format, compile=compile,
-                   quaternion_manifold=quaternion_manifold, constant_cameras=constant_cameras)
+    if kind == _cse.SNAVELY_NO_DISTORTION_2_7_3:
+        cams = np.ascontiguousarray(cams[:, :7])
+    return program(cams, pts, ci, pi, obs, loss=loss, kind=kind, format=format, compile=compile,
+                   quaternion_manifold=quaternion_manifold, constant_cameras=constant_cameras,
+                   loss_data=loss_data)

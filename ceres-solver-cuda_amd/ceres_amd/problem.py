@@ -92,6 +92,10 @@ class ResidualGroup:
     data: np.ndarray           # (n, data size) float64
     index: Optional[np.ndarray] = None  # (n,) int64 program order; None = contiguous
     first: int = 0
+    # (n, 2) float64: each block's own loss parameters (a, scale); loss then
+    # gives the kind and `scaled` only (cse_residual_group.loss_data_size 2).
+    # None = loss.a and loss.scale hold for every block.
+    loss_data: Optional[np.ndarray] = None
 
     @property
     def n(self):
@@ -279,6 +283,10 @@ class Program:
         for k, g in enumerate(self.groups):
             ids = np.ascontiguousarray(g.ids, np.int32)
             data = np.ascontiguousarray(g.data, np.float64)
+            if g.loss_data is not None:  # the rows widened by the block's (a, scale)
+                ld = np.asarray(g.loss_data, np.float64).reshape(g.n, 2)
+                data = np.ascontiguousarray(np.concatenate([data.reshape(g.n, -1), ld], axis=1))
+                groups[k].loss_data_size = 2
             idx = None if g.index is None else np.ascontiguousarray(g.index, np.int64)
             keep += [ids, data, idx]
             groups[k].functor_kind = g.kind
@@ -371,7 +379,11 @@ class ProblemCUDA:
         self._tangent[b] = self._sizes[b] - 1
         self._manifold[b] = _cse.MANIFOLD_QUATERNION_EUCLIDEAN
 
-    def add_residual_blocks(self, kind, loss, ids, data):
+    def add_residual_blocks(self, kind, loss, ids, data, loss_data=None):
+        """loss_data: (n, 2) per-block loss parameters (a, scale) for the whole
+        batch, e.g. per-observation weights with Loss.huber(1).scaled_by(1):
+        `loss` then gives the loss kind and `scaled` only.  Library losses on
+        library kinds."""
         ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1, len(functor_shape(kind)[1])))
         data = np.ascontiguousarray(np.asarray(data, np.float64).reshape(ids.shape[0], -1))
         n = ids.shape[0]
@@ -385,16 +397,32 @@ class ProblemCUDA:
             if dup.size:
                 raise ValueError(f"add_residual_blocks: duplicate parameter blocks in residual "
                                  f"block {self._nrb + int(dup[0])}: {ids[dup[0]].tolist()}")
-        self._groups.append(ResidualGroup(kind, loss or Loss.trivial(), ids, data, None, self._nrb))
+        loss = loss or Loss.trivial()
+        if loss_data is not None:
+            loss_data = np.ascontiguousarray(np.asarray(loss_data, np.float64).reshape(n, 2))
+            if loss.kind == _cse.LOSS_USER or kind >= _cse.FUNCTOR_USER_FIRST:
+                raise ValueError("add_residual_blocks: per-block loss parameters need a library "
+                                 "loss on a library functor kind")
+            if loss.kind == _cse.LOSS_TRIVIAL and not loss.scaled:
+                raise ValueError("add_residual_blocks: per-block parameters of the unscaled "
+                                 "trivial loss (nothing varies)")
+        self._groups.append(ResidualGroup(kind, loss, ids, data, None, self._nrb, loss_data))
         self._nrb += n
         return range(self._nrb - n, self._nrb)
 
     def add_residual_block(self, kind, loss, data, *blocks):
         return self.add_residual_blocks(kind, loss, [blocks], [data])[0]
 
-    def program(self, group_by_type=True, reduce=True):
+    def program(self, group_by_type=True, reduce=True, merge_loss_parameters=False):
         """Program order = insertion order.  Blocks sharing (kind, loss) are
         merged into one group, like the per-type evaluator registry.
+
+        merge_loss_parameters: group by the loss *type* -- (kind, loss.kind,
+        loss.scaled) -- for library losses on library kinds; a merged group
+        whose blocks differ in (a, scale) carries them per block
+        (ResidualGroup.loss_data, program order), one whose blocks all agree
+        stays a plain uniform group.  User losses and user kinds keep the
+        by-value key.  Default False: one group per distinct loss value.
 
         reduce: drop residual blocks whose parameter blocks are all constant,
         as Program::CreateReducedProgram does before evaluation
@@ -407,23 +435,48 @@ class ProblemCUDA:
             for g in groups:
                 live = ~np.all(const_flags[g.ids] != 0, axis=1)
                 if live.any():
-                    kept.append(ResidualGroup(g.kind, g.loss, g.ids[live], g.data[live], None, nrb))
+                    kept.append(ResidualGroup(g.kind, g.loss, g.ids[live], g.data[live], None, nrb,
+                                              None if g.loss_data is None else g.loss_data[live]))
                     nrb += int(live.sum())
             groups = kept
         else:
             nrb = self._nrb
         if group_by_type:
             merged = {}
-            for g in groups:
-                key = (g.kind,) + g.loss.key()
-                idx = np.arange(g.first, g.first + g.n, dtype=np.int64)
-                if key in merged:
-                    m = merged[key]
-                    m.ids = np.concatenate([m.ids, g.ids])
-                    m.data = np.concatenate([m.data, g.data])
-                    m.index = np.concatenate([m.index, idx])
+            parts = {}  # key -> per-batch lists, concatenated once below
+            for serial, g in enumerate(groups):
+                by_type = (merge_loss_parameters and g.loss.kind != _cse.LOSS_USER and
+                           g.kind < _cse.FUNCTOR_USER_FIRST and
+                           (g.loss.kind != _cse.LOSS_TRIVIAL or g.loss.scaled))
+                if by_type:
+                    key = (g.kind, g.loss.kind, bool(g.loss.scaled))
+                elif g.loss_data is not None:
+                    key = (g.kind, "batch", serial)  # a per-block batch stays its own group
                 else:
-                    merged[key] = ResidualGroup(g.kind, g.loss, g.ids, g.data, idx, 0)
+                    key = (g.kind,) + g.loss.key()
+                idx = np.arange(g.first, g.first + g.n, dtype=np.int64)
+                ld = g.loss_data
+                if by_type and ld is None:
+                    ld = np.tile(np.array([[g.loss.a, g.loss.scale if g.loss.scaled else 1.0]]), (g.n, 1))
+                if key not in merged:
+                    merged[key] = ResidualGroup(g.kind, g.loss, None, None, None, 0)
+                    parts[key] = ([], [], [], [])
+                for lst, v in zip(parts[key], (g.ids, g.data, idx, ld)):
+                    lst.append(v)
+            for key, m in merged.items():
+                ids, data, index, ld = parts[key]
+                m.ids, m.data, m.index = np.concatenate(ids), np.concatenate(data), np.concatenate(index)
+                if ld[0] is not None:
+                    m.loss_data = np.concatenate(ld)
+                    # the columns the loss type reads: a (Huber, Cauchy), scale (scaled)
+                    cols = [c for c, read in ((0, m.loss.kind != _cse.LOSS_TRIVIAL), (1, m.loss.scaled))
+                            if read]
+                    if (m.n and len(key) == 3 and key[1] != "batch" and
+                            (m.loss_data[:, cols] == m.loss_data[0, cols]).all()):
+                        # all blocks agree: a plain uniform group
+                        m.loss = Loss(m.loss.kind, float(m.loss_data[0, 0]) if 0 in cols else m.loss.a,
+                                      m.loss.scaled, float(m.loss_data[0, 1]) if 1 in cols else m.loss.scale)
+                        m.loss_data = None
             groups = list(merged.values())
             for g in groups:
                 if np.array_equal(g.index, np.arange(g.index[0], g.index[0] + g.n)):

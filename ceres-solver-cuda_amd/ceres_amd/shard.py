@@ -106,15 +106,18 @@ def gradient_maps(shard, num_points, num_cameras, cam_size=9, pt_size=3):
 
 def shard_program(cameras, points, cam_idx, pt_idx, obs, rank, world, loss=None,
                   format=BLOCK_SPARSE, compile=True, quaternion_manifold=False,
-                  constant_cameras=()):
+                  constant_cameras=(), loss_data=None):
     """The rank's Program: its points (renumbered from 0), every camera, its
-    observations; same functor, loss and camera manifold as the full problem."""
+    observations; same functor, loss and camera manifold as the full problem.
+    loss_data: the full problem's per-block loss parameters (bal.program),
+    sliced with the observations."""
     pc, bc = point_bucket_cuts(pt_idx, points.shape[0], world)
     p0, p1, b0, b1 = pc[rank], pc[rank + 1], bc[rank], bc[rank + 1]
     prog = bal.program(cameras, points[p0:p1], cam_idx[b0:b1],
                        np.asarray(pt_idx[b0:b1]) - p0, obs[b0:b1], loss=loss, format=format,
                        compile=compile, quaternion_manifold=quaternion_manifold,
-                       constant_cameras=constant_cameras)
+                       constant_cameras=constant_cameras,
+                       loss_data=None if loss_data is None else np.asarray(loss_data)[b0:b1])
     f_cells = None
     if len(constant_cameras):
         active = ~np.isin(np.asarray(cam_idx), np.asarray(constant_cameras))

@@ -28,8 +28,10 @@
 #include "../../include/cse.h"
 #include "group_store_kernel.hpp"
 #include "jet_kernels.h"
+#include "kernel_pickers.hpp"
 #include "launch.hpp"
 #include "multi_device.h"
+#include "per_block_loss_kernels.h"
 #include "plan.hpp"
 #include "schur_kernels.hpp"
 
@@ -44,6 +46,23 @@ using cse::kAffinePacked;
 using cse::kKindQuaternionTangent;
 using cse::kTable;
 using cse::KindShape;
+using cse::LaunchFn;
+using cse::VisitKind;
+using cse::VisitSlot0Size;
+using TestLinear3_234 = cse::TestLinear3_234;
+using TestLinear3_432 = cse::TestLinear3_432;
+using TestLinear2_23 = cse::TestLinear2_23;
+using TestLinear3_24 = cse::TestLinear3_24;
+using TestLinear4_34 = cse::TestLinear4_34;
+
+// The uniform-loss pickers (kernel_pickers.hpp); a group with per-block loss
+// parameters takes cse::PerBlockPick / PerBlockPickFused instead.
+LaunchFn Pick(int kind, int loss, bool jac, int policy, bool dma, bool const0 = false) {
+  return cse::Pick<cse::UniformLosses>(kind, loss, jac, policy, dma, const0);
+}
+LaunchFn PickFused(int kind, int loss, int policy, bool points, bool const0 = false) {
+  return cse::PickFused<cse::UniformLosses>(kind, loss, policy, points, const0);
+}
 
 int Fail(int code, const std::string& msg) { return CseFail(code, msg); }
 
@@ -63,35 +82,6 @@ int Fail(int code, const std::string& msg) { return CseFail(code, msg); }
       return Fail(CSE_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-// The functor kinds the library is built for.  Visit(kind, f) calls
-// f(K{}) with the kind's functor type; returns false for an unknown kind.
-using TestLinear3_234 = cse::LinearTestKind<3, 2, 3, 4>;
-using TestLinear3_432 = cse::LinearTestKind<3, 4, 3, 2>;
-using TestLinear2_23 = cse::LinearTestKind<2, 2, 3>;
-using TestLinear3_24 = cse::LinearTestKind<3, 2, 4>;
-using TestLinear4_34 = cse::LinearTestKind<4, 3, 4>;
-
-// (kKindQuaternionTangent, plan.hpp: the internal kernel kind of a group
-// whose slot-0 blocks are on CSE_MANIFOLD_QUATERNION_EUCLIDEAN.)
-template <class F>
-bool VisitKind(int kind, F&& f) {
-  switch (kind) {
-    case kKindQuaternionTangent: f(cse::SnavelyQuaternionTangentKind{}); return true;
-    case CSE_FUNCTOR_SNAVELY_2_9_3: f(cse::SnavelyKind{}); return true;
-    case CSE_FUNCTOR_SNAVELY_NO_DISTORTION_2_7_3: f(cse::SnavelyNoDistortionKind{}); return true;
-    case CSE_FUNCTOR_SNAVELY_QUATERNION_2_10_3: f(cse::SnavelyQuaternionKind{}); return true;
-    case CSE_FUNCTOR_POINT_DISPLACEMENT_3_3: f(cse::PointDisplacementKind{}); return true;
-    case CSE_FUNCTOR_TEST_LINEAR_3_2_3_4: f(TestLinear3_234{}); return true;
-    case CSE_FUNCTOR_TEST_LINEAR_3_4_3_2: f(TestLinear3_432{}); return true;
-    case CSE_FUNCTOR_TEST_LINEAR_2_2_3: f(TestLinear2_23{}); return true;
-    case CSE_FUNCTOR_TEST_LINEAR_3_2_4: f(TestLinear3_24{}); return true;
-    case CSE_FUNCTOR_TEST_LINEAR_4_3_4: f(TestLinear4_34{}); return true;
-    case CSE_FUNCTOR_TEST_BILINEAR_1_2_2: f(cse::BilinearTestKind{}); return true;
-    case CSE_FUNCTOR_TEST_TEN_PARAMETER_1_x10: f(cse::TenParameterTestKind{}); return true;
-    case CSE_FUNCTOR_TEST_PARTIAL_OUTPUT_2_1: f(cse::PartialOutputTestKind{}); return true;
-    default: return false;
-  }
-}
 
 // The planner's shape table (plan.hpp, cse::kKindRows) row by row against
 // the functor types the kernels are instantiated with.
@@ -208,7 +198,8 @@ struct DevBuf {
 struct Group : cse::GroupPlan {
   std::string user_name;
   DevBuf<int32_t> ids;
-  DevBuf<double> data;
+  DevBuf<double> data;       // [n][D]: the functor constants alone
+  DevBuf<double> loss_data;  // [n][2] (a, scale) records: per-block loss parameters only
   DevBuf<int64_t> gindex;  // only when not contiguous
   DevBuf<double> packed0;  // repacked slot-0 table (repack0)
   // Gradient post-pass plan per slot (cse::GradPlanInfo, cse::GradTables).
@@ -240,7 +231,6 @@ struct Group : cse::GroupPlan {
   DevBuf<int64_t> runs;
 };
 
-using LaunchFn = void (*)(const cse::GroupArgs&, int64_t num_wg, hipStream_t);
 
 // Waves per workgroup of the CGNR and Schur chunk kernels (one chunk per
 // wave either way); one wave per workgroup, as the Jacobian kernels are
@@ -254,199 +244,10 @@ constexpr int kOperatorWavesPerWg = cse::kWavesPerBlock;
 constexpr int64_t kPartialsTwoPass = 4096;
 constexpr int kPartialBlocks = 128;
 
-template <class K, int L, bool J>
-void LaunchTable(const cse::GroupArgs& a, int64_t num_wg, hipStream_t s) {
-  cse::LaunchTableKernel<K, L, J>(a, num_wg, s);
-}
-
-// The affine kernel: one 64-block chunk per wave, 4 waves per workgroup
-// (the residual-only and cost-only evaluations; one wave per workgroup
-// measured 1 % slower for them, profiles/round3/w1).
-template <class K, int L, bool J, bool Crs, int Co, class T = cse::ShippedTune>
-void LaunchChunks(const cse::GroupArgs& a, int64_t num_wg, hipStream_t s) {
-  cse::LaunchAffineChunks<K, L, J, Crs, Co, T>(a, num_wg, s);
-}
-
-// The BSM residual+Jacobian evaluation of two-slot kinds: one wave per
-// workgroup (EvaluateAffineChunksTwoRoundW1); the Snavely camera's, when
-// its outputs sit on 64-byte sectors, four-wave workgroups storing long
-// runs (EvaluateAffineChunksGroupStore, group_store_kernel.hpp).
-template <class K, class T>
-constexpr bool kGroupStore = std::is_same<K, cse::SnavelyKind>::value &&
-                             std::is_same<T, cse::ShippedTune>::value;
-
-template <class K, int L, int Co, class T = cse::ShippedTune>
-void LaunchTwoRound(const cse::GroupArgs& a, int64_t num_wg, hipStream_t s) {
-  (void)num_wg;
-  if constexpr (kGroupStore<K, T> && Co == 2) {
-    if (cse::GroupStoreEligible(a)) {
-      const int64_t chunks = cse::Chunks(a.n);
-      hipLaunchKernelGGL((cse::EvaluateAffineChunksGroupStore<K, L>),
-                         dim3((unsigned)((chunks + cse::kQuadWaves - 1) / cse::kQuadWaves)),
-                         dim3(cse::kQuadWaves * cse::kWave), 0, s, a);
-      return;
-    }
-  }
-  cse::LaunchTwoRoundW1<K, L, Co, T>(a, s);
-}
-
-// The CRS residual+Jacobian evaluation: one wave per workgroup.
-template <class K, int L, int Co, class T = cse::ShippedTune>
-void LaunchTwoRoundCrs(const cse::GroupArgs& a, int64_t num_wg, hipStream_t s) {
-  (void)num_wg;
-  cse::LaunchTwoRoundCrsW1<K, L, Co, T>(a, s);
-}
-
-// The affine kernel with the fused gradient (Snavely groups): with the
-// slot-0 contributions (gradient_mode 3) or points only (gradient_mode 0,
-// slot 0 from CameraGradientKernel; one wave per workgroup).
-template <class K, int L, bool Crs, class T = cse::ShippedTune>
-void LaunchFused(const cse::GroupArgs& a, int64_t num_wg, hipStream_t s) {
-  hipLaunchKernelGGL((cse::EvaluateAffineChunksFused<K, L, Crs, T>), dim3((unsigned)num_wg),
-                     dim3(cse::kBlockThreads), 0, s, a);
-}
-template <class K, int L, bool Crs, class T = cse::PointsOnlyTune>
-void LaunchFusedPoints(const cse::GroupArgs& a, int64_t num_wg, hipStream_t s) {
-  (void)num_wg;
-  hipLaunchKernelGGL((cse::EvaluateAffineChunksFusedPointsW1<K, L, Crs, T>), dim3((unsigned)cse::Chunks(a.n)),
-                     dim3(cse::kWave), 0, s, a);
-}
-
 using cse::FusedKind;
 bool SnavelyShaped(const Group& G) { return cse::SnavelyShaped(G.shape); }
 bool UserFused(const Group& G) { return cse::UserFused(G.user, G.shape); }
 
-// f(std::integral_constant<int, s0>) for the slot-0 sizes the fused
-// gradient's tail is built for (1..16, the affine kernels' bound).
-template <class F>
-bool VisitSlot0Size(int s0, F&& f) {
-  switch (s0) {
-#define CSE_S0_CASE(n) \
-  case n: f(std::integral_constant<int, n>{}); return true;
-    CSE_S0_CASE(1) CSE_S0_CASE(2) CSE_S0_CASE(3) CSE_S0_CASE(4) CSE_S0_CASE(5) CSE_S0_CASE(6)
-    CSE_S0_CASE(7) CSE_S0_CASE(8) CSE_S0_CASE(9) CSE_S0_CASE(10) CSE_S0_CASE(11) CSE_S0_CASE(12)
-    CSE_S0_CASE(13) CSE_S0_CASE(14) CSE_S0_CASE(15) CSE_S0_CASE(16)
-#undef CSE_S0_CASE
-    default: return false;
-  }
-}
-
-// f(std::integral_constant<int, L>) with the kernels' loss template argument
-// of a cse_loss kind: Huber, Cauchy, and the trivial loss for every other.
-template <class F>
-auto VisitLoss(int loss, F&& f) {
-  switch (loss) {
-    case CSE_LOSS_HUBER: return f(std::integral_constant<int, cse::kLossHuber>{});
-    case CSE_LOSS_CAUCHY: return f(std::integral_constant<int, cse::kLossCauchy>{});
-    default: return f(std::integral_constant<int, cse::kLossTrivial>{});
-  }
-}
-
-template <class K>
-LaunchFn PickFusedK(int loss, bool crs, bool points) {
-  return VisitLoss(loss, [&](auto l) -> LaunchFn {
-    constexpr int L = decltype(l)::value;
-    return points ? (crs ? &LaunchFusedPoints<K, L, true> : &LaunchFusedPoints<K, L, false>)
-                  : (crs ? &LaunchFused<K, L, true> : &LaunchFused<K, L, false>);
-  });
-}
-
-template <class K, bool Crs>
-LaunchFn PickFusedC0(int loss, bool points) {
-  using TP = cse::PointsOnlyTuneC0;
-  using TF = cse::ShippedTuneC0;
-  return VisitLoss(loss, [&](auto l) -> LaunchFn {
-    constexpr int L = decltype(l)::value;
-    return points ? &LaunchFusedPoints<K, L, Crs, TP> : &LaunchFused<K, L, Crs, TF>;
-  });
-}
-
-// points = true: the slot-1 rows only (gradient_mode 0, slot 0 from
-// CameraGradientKernel); false: with the slot-0 contributions (mode 3).
-// const0: groups with constant slot-0 blocks (BSM).
-LaunchFn PickFused(int kind, int loss, int policy, bool points, bool const0 = false) {
-  const bool crs = policy == kAffineCrs;
-  if (const0) {
-    if (kind == kKindQuaternionTangent)
-      return crs ? PickFusedC0<cse::SnavelyQuaternionTangentKind, true>(loss, points)
-                 : PickFusedC0<cse::SnavelyQuaternionTangentKind, false>(loss, points);
-    return crs ? PickFusedC0<cse::SnavelyKind, true>(loss, points)
-               : PickFusedC0<cse::SnavelyKind, false>(loss, points);
-  }
-  if (kind == kKindQuaternionTangent)
-    return PickFusedK<cse::SnavelyQuaternionTangentKind>(loss, crs, points);
-  return PickFusedK<cse::SnavelyKind>(loss, crs, points);
-}
-
-// Affine kernels: cooperative slot-0 gather by LDS-DMA from the repacked
-// table (dma = true) or by 8-byte pieces straight from the state.
-template <class K, int L, bool Crs>
-LaunchFn PickAffine(bool jac, bool dma) {
-  if constexpr (!Crs && cse::kTwoRoundBsm<K>) {
-    // (the 8-byte-piece gather of kCoop 1 would spill at 128 VGPRs)
-    if (jac && dma) return &LaunchTwoRound<K, L, 2>;
-  }
-  if constexpr (Crs) {
-    // 1778 CRS 0.298 -> 0.285 ms, 13682 CRS 1.540 -> 1.480 ms (profiles/round2/s5k)
-    if (jac && dma) return &LaunchTwoRoundCrs<K, L, 2>;
-  }
-  if (dma) return jac ? &LaunchChunks<K, L, true, Crs, 2> : &LaunchChunks<K, L, false, Crs, 2>;
-  return jac ? &LaunchChunks<K, L, true, Crs, 1> : &LaunchChunks<K, L, false, Crs, 1>;
-}
-
-template <class K, int L>
-LaunchFn PickJP(bool jac, int policy, bool dma) {
-  if constexpr (cse::KindTraits<K>::NB <= 2 && cse::KindTraits<K>::NR <= 3) {
-    switch (policy) {
-      case kAffinePacked: return PickAffine<K, L, false>(jac, dma);
-      case kAffineCrs: return PickAffine<K, L, true>(jac, dma);
-      default: break;
-    }
-  }
-  return jac ? &LaunchTable<K, L, true> : &LaunchTable<K, L, false>;
-}
-
-// const0: the group has constant slot-0 blocks (FusedKind kinds, the
-// repacked table; DetectAffine): the Jacobian kernel with the packed F cells
-// (BSM) or the packed row blocks of two widths (CRS).
-LaunchFn PickConst0(int kind, int loss, bool jac, bool crs) {
-  auto pick = [&](auto kd) -> LaunchFn {
-    using K = decltype(kd);
-    using T = cse::ShippedTuneC0;
-    if (!jac) return nullptr;  // residual/cost kernels write no Jacobian: the usual ones
-    return VisitLoss(loss, [&](auto l) -> LaunchFn {
-      constexpr int L = decltype(l)::value;
-      return crs ? &LaunchTwoRoundCrs<K, L, 2, T> : &LaunchTwoRound<K, L, 2, T>;
-    });
-  };
-  if (kind == kKindQuaternionTangent) return pick(cse::SnavelyQuaternionTangentKind{});
-  if (kind == CSE_FUNCTOR_SNAVELY_2_9_3) return pick(cse::SnavelyKind{});
-  return nullptr;
-}
-
-LaunchFn Pick(int kind, int loss, bool jac, int policy, bool dma, bool const0 = false) {
-  if (const0 && jac)
-    return (policy == kAffinePacked || policy == kAffineCrs) && dma
-               ? PickConst0(kind, loss, jac, policy == kAffineCrs)
-               : nullptr;
-  LaunchFn fn = nullptr;
-  VisitKind(kind, [&](auto kd) {
-    using K = decltype(kd);
-    if constexpr (cse::AffineOnly<K>::value) {
-      if (policy == kAffinePacked || policy == kAffineCrs)
-        fn = VisitLoss(loss, [&](auto l) -> LaunchFn {
-          constexpr int L = decltype(l)::value;
-          return policy == kAffineCrs ? PickAffine<K, L, true>(jac, dma) : PickAffine<K, L, false>(jac, dma);
-        });
-    } else if constexpr (cse::TestOnly<K>::value) {
-      if (loss == CSE_LOSS_TRIVIAL)
-        fn = jac ? &LaunchTable<K, cse::kLossTrivial, true> : &LaunchTable<K, cse::kLossTrivial, false>;
-    } else {
-      fn = VisitLoss(loss, [&](auto l) -> LaunchFn { return PickJP<K, decltype(l)::value>(jac, policy, dma); });
-    }
-  });
-  return fn;
-}
 
 }  // namespace
 
@@ -582,6 +383,7 @@ cse::GroupArgs MakeArgs(cse_evaluator* ev, Group& G, const double* state, double
   a.plain0 = G.plain0 ? 1 : 0;
   a.plain0_state_base = G.plain0_state_base;
   a.plain0_delta_base = G.plain0_delta_base;
+  a.loss_data = G.loss_data.p;
   return a;
 }
 
@@ -675,6 +477,8 @@ int LaunchCameraGradKernel(cse_evaluator* ev, Group& G, const double* state, hip
   cg.loss.scale = G.loss.scale;
   cg.loss.scaled = G.loss.scaled;
   cg.apply_loss = ev->opts.apply_loss_function;
+  cg.loss_data = G.loss_data.p;  // records in the blocks' original order: through the plan's perm
+  cg.perm = P.perm.p;
   if (G.const0) {  // active cameras' state offsets need not be affine
     cg.packed0 = G.packed0.p;
     cg.packed_lo = G.slot0_lo;
@@ -688,18 +492,11 @@ int LaunchCameraGradKernel(cse_evaluator* ev, Group& G, const double* state, hip
     return CSE_OK;
   }
   constexpr int W = kCamGradWavesPerWg;
-  const dim3 grid((unsigned)((cg.nslots + W - 1) / W));
+  static_assert(W == cse::kPerBlockCamGradWaves, "the per-block launch takes the same workgroups");
   if (P.nchunks > 0) {
-    auto launch = [&](auto kd) {
-      using K = decltype(kd);
-      VisitLoss(G.loss.kind, [&](auto l) {
-        hipLaunchKernelGGL((cse::CameraGradientKernel<K, decltype(l)::value, W>), grid,
-                           dim3(W * cse::kWave), 0, s, cg);
-      });
-    };
     if (G.jet) cse::LaunchJetCameraGradient(G.loss.kind, cg, cg.nslots, s);
-    else if (G.kind == kKindQuaternionTangent) launch(cse::SnavelyQuaternionTangentKind{});
-    else launch(cse::SnavelyKind{});
+    else if (G.loss_data_size) cse::LaunchPerBlockCameraGradient(G.kind, G.loss.kind, cg, s);
+    else cse::LaunchCameraGradientOf<cse::UniformLosses, W>(G.kind, G.loss.kind, cg, s);
   }
   CSE_HIP(hipGetLastError());
   return CSE_OK;
@@ -768,7 +565,24 @@ int UploadGroup(const cse_residual_group& g, const cse::GroupTables& T, Group* G
   }
   if ((rc = G.runs.upload(T.runs.data(), T.runs.size(), s))) return rc;
   if ((rc = G.ids.upload(g.parameter_block_ids, (size_t)g.num_blocks * k.nb, s))) return rc;
-  if ((rc = G.data.upload(g.functor_data, (size_t)g.num_blocks * k.data, s))) return rc;
+  // Per-block loss parameters: the rows de-interleaved, so that the kernels'
+  // functor data keeps its [n][D] form and the (a, scale) records are one
+  // aligned 16-byte load each.  (The host copies live until the wait below.)
+  std::vector<double> rows, records;
+  if (G.loss_data_size) {
+    const int64_t n = g.num_blocks, D = k.data, W = D + G.loss_data_size;
+    rows.resize((size_t)(n * D));
+    records.resize((size_t)(n * 2));
+    for (int64_t i = 0; i < n; ++i) {
+      for (int64_t c = 0; c < D; ++c) rows[i * D + c] = g.functor_data[i * W + c];
+      records[2 * i] = g.functor_data[i * W + D];
+      records[2 * i + 1] = g.functor_data[i * W + D + 1];
+    }
+    if ((rc = G.data.upload(rows.data(), rows.size(), s))) return rc;
+    if ((rc = G.loss_data.upload(records.data(), records.size(), s))) return rc;
+  } else if ((rc = G.data.upload(g.functor_data, (size_t)g.num_blocks * k.data, s))) {
+    return rc;
+  }
   if ((!G.affine || G.const0) && g.residual_block_index &&
       (rc = G.gindex.upload(g.residual_block_index, (size_t)g.num_blocks, s)))
     return rc;
@@ -858,7 +672,8 @@ int Enqueue(cse_evaluator* ev, const double* d_state, double* d_cost, double* d_
                                : G.user->affine[G.policy == kAffineCrs][jets ? 1 : 0][dma ? 1 : 0];
       if (!ufn) return Fail(CSE_ERR_UNSUPPORTED, "user functor kind " + G.user_name + " has no such kernel");
     } else {
-      fn = Pick(G.kind, G.loss.kind, jets, G.policy, dma, G.const0);
+      fn = G.loss_data_size ? cse::PerBlockPick(G.kind, G.loss.kind, jets, G.policy, dma, G.const0)
+                            : Pick(G.kind, G.loss.kind, jets, G.policy, dma, G.const0);
       if (G.jet && jets)  // the Jet<double, 12> instantiations (cse_create kept only these shapes)
         fn = G.policy == kTable ? cse::JetSnavelyTable(G.loss.kind)
                                 : cse::JetSnavelyJacobian(G.loss.kind, G.policy == kAffineCrs);
@@ -878,7 +693,8 @@ int Enqueue(cse_evaluator* ev, const double* d_state, double* d_cost, double* d_
       if (G.user)
         ufn = G.user->fused_points[G.policy == kAffineCrs];
       else
-        fn = PickFused(G.kind, G.loss.kind, G.policy, recompute, G.const0);
+        fn = G.loss_data_size ? cse::PerBlockPickFused(G.kind, G.loss.kind, G.policy, recompute, G.const0)
+                              : PickFused(G.kind, G.loss.kind, G.policy, recompute, G.const0);
       if (G.jet) fn = cse::JetSnavelyFusedPoints(G.loss.kind, G.policy == kAffineCrs);
     }
     if (timing.first && g == 0) CSE_HIP(hipEventRecord(timing.first, ev->stream));
@@ -1006,6 +822,8 @@ int cse_create(const cse_problem_desc* d, const cse_options* options, cse_evalua
   if (ev->opts.jacobian_form != CSE_JACOBIAN_CLOSED_FORM && ev->opts.jacobian_form != CSE_JACOBIAN_JET)
     return bail(Fail(CSE_ERR_INVALID, "jacobian_form " + std::to_string(ev->opts.jacobian_form) +
                                           " is not a cse_jacobian_form"));
+  // (before the device is picked: a descriptor these refuse needs no GPU)
+  if ((rc = cse::ValidateLossData(d, &ev->opts))) return bail(rc);
 
   if (ev->opts.device >= 0) {
     const hipError_t e = hipSetDevice(ev->opts.device);
@@ -1039,7 +857,7 @@ int cse_create(const cse_problem_desc* d, const cse_options* options, cse_evalua
   // Validate, then plan and upload one group at a time: a group's host
   // tables (UploadGroup waits for their copies) die before the next is planned.
   cse::ProgramPlan P;
-  if ((rc = cse::ValidateGroups(d, &CseUserKind, &P))) return bail(rc);
+  if ((rc = cse::ValidateGroups(d, &CseUserKind, &P, &ev->opts))) return bail(rc);
   ev->has_layout = P.has_layout;
   ev->groups.resize((size_t)d->num_groups);
   for (int gi = 0; gi < d->num_groups; ++gi) {
@@ -1799,3 +1617,9 @@ int cse_reset_kernel_stats(cse_evaluator* ev) {
 }
 
 }  // extern "C"
+
+// The asan build keeps the per-block loss kernels in this object (its link
+// line, tests/cpp/Makefile, lists the objects of ABI 5).
+#ifdef CSE_PER_BLOCK_LOSS_IN_THIS_TU
+#include "per_block_loss_kernels.hip"
+#endif

@@ -682,6 +682,10 @@ __device__ __forceinline__ void AffineChunkBody(const GroupArgs& a) {
   }
 
   AffineInputs<K> in;
+  // The block's loss record (per-block kinds), beside its id and data loads:
+  // non-temporal where the gather's data loads are (kCoop 2).
+  LossParams lp;
+  LoadBlockLoss<kLoss, kCoop == 2>(a, i, &lp);
   if constexpr (kCoop == 2) {
     int2 id;
     if constexpr (Tr::NB == 2) {
@@ -718,7 +722,7 @@ __device__ __forceinline__ void AffineChunkBody(const GroupArgs& a) {
     ok = !bad;
   }
   const double cost =
-      LossAndCorrect<K, kLoss, kJac>(a.loss, a.apply_loss, r, J0, J1, a.residuals != nullptr,
+      LossAndCorrect<K, kLoss, kJac>(LossOf<kLoss>(a, lp), a.apply_loss, r, J0, J1, a.residuals != nullptr,
                                      a.user_loss);
   bool act0 = true;  // slot-0 block active (T::kConst0: from its bit)
   if constexpr (T::kConst0) {
@@ -1318,6 +1322,11 @@ struct CamGradArgs {
   int32_t packed_lo;
   int32_t packed_stride;
   double user_loss[kUserLossDoubles];  // a user kind's loss object (kLossUser)
+  // Per-block loss kinds: the group's records (GroupArgs::loss_data) in the
+  // blocks' original order, and the slot-0-sorted position -> original index
+  // map (the plan's perm; null = identity).
+  const double* loss_data;
+  const int32_t* perm;
 };
 
 // r and the slot-0 Jacobian (NR x S0, row-major) of one block, the slot-1
@@ -1394,8 +1403,12 @@ CameraGradientKernel(const CamGradArgs g) {
       qb[u] = live[u] ? q + u * kWave : q;
     }
     double d[kU][D], x1[kU][S1];
+    LossParams lp[kU];
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
+      if constexpr (IsPerBlockLoss(kLoss))  // the record of the block's original index
+        LoadBlockLoss<kLoss, false>(g, g.perm ? (int64_t)__builtin_nontemporal_load(g.perm + qb[u]) : qb[u],
+                                    &lp[u]);
 #pragma unroll
       for (int k = 0; k < D; ++k) d[u][k] = __builtin_nontemporal_load(g.sdata + qb[u] * D + k);
       const int32_t id1 = __builtin_nontemporal_load(g.sid1 + qb[u]);
@@ -1409,7 +1422,7 @@ CameraGradientKernel(const CamGradArgs g) {
       EvaluateSlot0<K>(d[u], x0, x1[u], r, J0);
 #pragma unroll
       for (int k = 0; k < NR * S1p; ++k) J1[k] = 0.0;
-      LossAndCorrect<K, kLoss, true>(g.loss, g.apply_loss, r, J0, J1, true, g.user_loss);
+      LossAndCorrect<K, kLoss, true>(LossOf<kLoss>(g, lp[u]), g.apply_loss, r, J0, J1, true, g.user_loss);
       if (live[u]) {
 #pragma unroll
         for (int c = 0; c < S0; ++c) {
@@ -1666,6 +1679,9 @@ __global__ __launch_bounds__(kBlockThreads) void EvaluateTableKernel(const Group
     double d[D];
 #pragma unroll
     for (int k = 0; k < D; ++k) d[k] = a.data[i * D + k];
+    LossParams own;
+    LoadBlockLoss<kLoss, false>(a, i, &own);
+    const LossParams& lp = LossOf<kLoss>(a, own);
     double x[N];
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
@@ -1761,12 +1777,12 @@ __global__ __launch_bounds__(kBlockThreads) void EvaluateTableKernel(const Group
       double sq = 0.0;
 #pragma unroll
       for (int k = 0; k < NR; ++k) sq += r[k] * r[k];
-      const bool robust = (kLoss != kLossTrivial || a.loss.scaled) && a.apply_loss;
+      const bool robust = (LossBase(kLoss) != kLossTrivial || lp.scaled) && a.apply_loss;
       if (!robust) {
         cost = 0.5 * sq;
       } else {
         double rho[3];
-        EvaluateLoss<kLoss, K>(a.loss, sq, rho, a.user_loss);
+        EvaluateLoss<LossBase(kLoss), K>(lp, sq, rho, a.user_loss);
         const Corrector corr(sq, rho);
         if constexpr (kJac) corr.template CorrectJacobian<NR, N>(r, J);
         corr.template CorrectResiduals<NR>(r);

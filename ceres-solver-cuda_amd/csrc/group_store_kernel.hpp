@@ -146,11 +146,13 @@ EvaluateAffineChunksGroupStore(const GroupArgs a) {
     AffineInputs<K> in;
     const long long b = __builtin_nontemporal_load(reinterpret_cast<const long long*>(a.ids) + i);
     const int2 id = make_int2((int)b, (int)(b >> 32));
+    LossParams lp;
+    LoadBlockLoss<kLoss>(a, i, &lp);
     GatherCoopDma<K>(a, i, id, &in, fw, lane);
     ok = EvaluateFunctor<K, true>(in.d, in.x0, in.x1, r, J0, J1);
     if (ok && a.check_finite)
       ok = !(AnyNonFinite<NR>(r) || AnyNonFinite<NR * S0>(J0) || AnyNonFinite<NR * S1>(J1));
-    cost = LossAndCorrect<K, kLoss, true>(a.loss, a.apply_loss, r, J0, J1, a.residuals != nullptr);
+    cost = LossAndCorrect<K, kLoss, true>(LossOf<kLoss>(a, lp), a.apply_loss, r, J0, J1, a.residuals != nullptr);
     if (a.gradient != nullptr && active) {  // gradient_mode 2: FP64 atomics, as the reference
       AddGradientSlot<NR, S0>(a.gradient + a.delta_base[0] + (int64_t)S0 * in.id0, S0, r, J0);
       AddGradientSlot<NR, S1p>(a.gradient + a.delta_base[1] + (int64_t)S1 * in.id1, S1, r, J1);

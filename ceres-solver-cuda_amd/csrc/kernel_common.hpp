@@ -82,12 +82,17 @@ struct GroupArgs {
   // its PbDev is formed from these, not loaded.
   int64_t plain0_state_base, plain0_delta_base;
   int32_t plain0;
+  // Per-block loss parameters (cse_residual_group.loss_data_size == 2):
+  // block i's (a, scale) at loss_data + 2 i, one 16-byte record, read by the
+  // per-block loss kinds (kLossPerBlock, loss.hpp); null for a uniform group,
+  // whose kernels read `loss` above.
+  const double* loss_data;
 };
 
 // Layout tag of the argument blocks (GroupArgs, GradArgs, CamGradArgs),
 // checked when a user functor kind registers kernels compiled in another TU
 // (cse_register_functor): bump on any change to them.
-constexpr uint64_t kGroupArgsTag = 0x6373654761310005ull;
+constexpr uint64_t kGroupArgsTag = 0x6373654761310006ull;
 
 // Compile-time shape of a functor kind: kR residuals, NB parameter blocks
 // of sizes kSizes[0..NB) concatenated into N columns.
@@ -335,12 +340,39 @@ CSE_HD bool EvaluateFunctorFlat(const double* d, const double* x, double* r, dou
   }
 }
 
+// The loss record of block i of a per-block kind into *own: its (a, scale),
+// one 16-byte load of loss_data + 2 i (non-temporal where the neighbouring
+// data loads are: the record is read once), with the group's `scaled`.
+// Callers issue it beside the block's id and data loads, so that it is in
+// flight during the gather and the functor.  A uniform kind loads nothing and
+// leaves *own alone (LossOf never reads it).  Args: GroupArgs or CamGradArgs.
+typedef double cse_v2d __attribute__((ext_vector_type(2)));
+template <int kLoss, bool kNt = true, class Args>
+__device__ __forceinline__ void LoadBlockLoss(const Args& a, int64_t i, LossParams* own) {
+  if constexpr (IsPerBlockLoss(kLoss)) {
+    const cse_v2d* p = reinterpret_cast<const cse_v2d*>(a.loss_data) + i;
+    const cse_v2d v = kNt ? __builtin_nontemporal_load(p) : *p;
+    own->a = v.x;
+    own->scale = v.y;
+    own->scaled = a.loss.scaled;
+  }
+}
+// The parameters the loss step takes: the group's (uniform kinds: a.loss
+// itself, as before per-block kinds existed) or the block's record.
+template <int kLoss, class Args>
+__device__ __forceinline__ const LossParams& LossOf(const Args& a, const LossParams& own) {
+  if constexpr (IsPerBlockLoss(kLoss)) return own;
+  else return a.loss;
+}
+
 // Loss and correction (cuda_evaluator_kernel.h:373-407 /
 // residual_block.cc:159-199) on r and the per-slot Jacobians J0 (kR x S0)
 // and J1 (kR x S1).  Returns the block cost.  correct = false (a cost-only
 // evaluation: no residual or Jacobian leaves the kernel) skips the
 // Corrector, as ResidualBlock::Evaluate's early exit does when neither
 // Jacobians nor residuals are output (residual_block.cc:175-179).
+// kLoss may be a per-block kind (kLossPerBlock): lp then holds the block's
+// own record (BlockLoss) and the arithmetic is its uniform twin's.
 template <class K, int kLoss, bool kJac>
 CSE_HD double LossAndCorrect(const LossParams& lp, bool apply_loss, double* r, double* J0,
                              double* J1, bool correct = true, const double* user_loss = nullptr) {
@@ -349,10 +381,10 @@ CSE_HD double LossAndCorrect(const LossParams& lp, bool apply_loss, double* r, d
   double sq = 0.0;
 #pragma unroll
   for (int k = 0; k < NR; ++k) sq += r[k] * r[k];
-  const bool robust = (kLoss != kLossTrivial || lp.scaled) && apply_loss;
+  const bool robust = (LossBase(kLoss) != kLossTrivial || lp.scaled) && apply_loss;
   if (!robust) return 0.5 * sq;
   double rho[3];
-  EvaluateLoss<kLoss, K>(lp, sq, rho, user_loss);
+  EvaluateLoss<LossBase(kLoss), K>(lp, sq, rho, user_loss);
   if (!kJac && !correct) return 0.5 * rho[0];
   const Corrector corr(sq, rho);
   if constexpr (kJac) {

@@ -19,6 +19,20 @@ namespace cse {
 enum LossKind { kLossTrivial = 0, kLossHuber = 1, kLossCauchy = 2, kLossUser = 3 };
 constexpr int kUserLossDoubles = 8;
 
+// Per-block forms of the library losses, further values of the kernels' loss
+// template argument: kLossPerBlock + the base kind.  The group's loss type
+// and `scaled` are uniform; each block brings its own (a, scale) record
+// (GroupArgs::loss_data).  The arithmetic is the base kind's (EvaluateLoss
+// is instantiated with LossBase), so equal parameters give equal bits.
+constexpr int kLossPerBlock = 4;
+enum PerBlockLossKind {
+  kLossTrivialPerBlock = kLossPerBlock + kLossTrivial,  // scaled only
+  kLossHuberPerBlock = kLossPerBlock + kLossHuber,
+  kLossCauchyPerBlock = kLossPerBlock + kLossCauchy,
+};
+constexpr bool IsPerBlockLoss(int loss) { return loss >= kLossPerBlock; }
+constexpr int LossBase(int loss) { return IsPerBlockLoss(loss) ? loss - kLossPerBlock : loss; }
+
 // The loss type a kind carries for kLossUser (K::UserLoss), else void.
 template <class K, class = void>
 struct UserLossOf {

@@ -293,7 +293,10 @@ int CreateShard(const cse_problem_desc* d, const cse_options* opts, CseMulti::Sh
   for (int gi = 0; gi < d->num_groups; ++gi) {
     const cse_residual_group& g = d->groups[gi];
     const Shape& k = shapes[gi];
-    const int ds = k.data;
+    // Row stride of functor_data: the kind's constants and, with per-block
+    // loss parameters, the block's (a, scale) after them; sg keeps
+    // loss_data_size.
+    const int ds = k.data + g.loss_data_size;
     cse_residual_group sg = g;
     ids_store.emplace_back();
     auto& id = ids_store.back();
@@ -443,7 +446,7 @@ int MultiCreate(const cse_problem_desc* d, const cse_options* options, const int
   std::vector<Shape> shapes(d->num_groups);
   {
     cse::ProgramPlan checked;
-    const int rc = cse::ValidateGroups(d, &CseUserKind, &checked);
+    const int rc = cse::ValidateGroups(d, &CseUserKind, &checked, &opts);
     if (rc) return rc;
     for (int gi = 0; gi < d->num_groups; ++gi)
       shapes[gi] = {checked.shapes[gi].nr, checked.shapes[gi].nb, checked.shapes[gi].data};

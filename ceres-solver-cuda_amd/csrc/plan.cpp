@@ -114,8 +114,33 @@ int Validate(const cse_problem_desc* d) {
   return CSE_OK;
 }
 
-int ValidateGroups(const cse_problem_desc* d, UserLookup lookup, ProgramPlan* P) {
+int ValidateLossData(const cse_problem_desc* d, const cse_options* opts) {
+  for (int gi = 0; gi < d->num_groups; ++gi) {
+    const cse_residual_group& g = d->groups[gi];
+    if (g.loss_data_size == 0) continue;
+    const std::string what = "group " + std::to_string(gi) + ": loss_data_size " +
+                             std::to_string(g.loss_data_size);
+    if (g.loss_data_size != 2) return Fail(CSE_ERR_INVALID, what + " is neither 0 nor 2");
+    if (g.loss.kind == CSE_LOSS_USER)
+      return Fail(CSE_ERR_UNSUPPORTED, what + " with the user loss kind (3): a user loss object has no per-block form");
+    if (g.functor_kind >= CSE_FUNCTOR_USER_FIRST)
+      return Fail(CSE_ERR_UNSUPPORTED, what + " with a user functor kind: its launch table has no "
+                                              "per-block loss kernels");
+    if (IsTestKind(g.functor_kind))
+      return Fail(CSE_ERR_UNSUPPORTED, what + " with a test functor kind");
+    if (g.loss.kind == CSE_LOSS_TRIVIAL && !g.loss.scaled)
+      return Fail(CSE_ERR_INVALID, what + " with the unscaled trivial loss: nothing varies per block");
+    if (opts && opts->jacobian_form == CSE_JACOBIAN_JET)
+      return Fail(CSE_ERR_UNSUPPORTED, what + " with the Jet jacobian_form: the Jet kernels have no "
+                                              "per-block loss form");
+  }
+  return CSE_OK;
+}
+
+int ValidateGroups(const cse_problem_desc* d, UserLookup lookup, ProgramPlan* P,
+                   const cse_options* opts) {
   *P = ProgramPlan{};
+  if (const int rc = ValidateLossData(d, opts)) return rc;
   P->has_layout = d->jacobian_per_residual_layout && d->jacobian_per_residual_offsets;
   P->shapes.resize((size_t)d->num_groups);
   P->users.assign((size_t)d->num_groups, nullptr);
@@ -193,7 +218,7 @@ int ValidateGroups(const cse_problem_desc* d, UserLookup lookup, ProgramPlan* P)
         }
       }
     }
-    const int64_t per_block = 8LL * k.data + 4LL * k.nb + 8LL * k.nr;
+    const int64_t per_block = 8LL * (k.data + g.loss_data_size) + 4LL * k.nb + 8LL * k.nr;
     P->bytes_res += per_block * g.num_blocks;
     P->bytes_jac += per_block * g.num_blocks;
   }
@@ -772,6 +797,7 @@ void PlanGroup(const cse_problem_desc* d, const cse_options& opts, int gi, Progr
   G.user = P->users[gi];
   G.shape = P->shapes[gi];
   G.loss = g.loss;
+  G.loss_data_size = g.loss_data_size;
   G.n = g.num_blocks;
   G.first = g.first_residual_block;
   const KindShape& k = G.shape;  // follows G.shape when the kind changes below

@@ -144,6 +144,9 @@ struct GroupPlan {
   const cse_functor_ops* user = nullptr;  // a registered user functor kind
   KindShape shape{};
   cse_loss loss{};
+  // Doubles of loss parameters at the end of each functor_data row (0 or 2,
+  // cse_residual_group.loss_data_size); no planning decision depends on it.
+  int loss_data_size = 0;
   int64_t n = 0;
   bool affine = false;
   int policy = 0;
@@ -237,7 +240,14 @@ struct ProgramPlan {
 int Validate(const cse_problem_desc* d);
 // Every group and every residual block of it; fills the ValidateGroups part
 // of the plan.  Nothing below may be called on a descriptor these two refuse.
-int ValidateGroups(const cse_problem_desc* d, UserLookup lookup, ProgramPlan* P);
+// Per-block loss parameters (cse_residual_group.loss_data_size): the library's
+// losses on the library's kinds, closed-form Jacobian.  Their values are not
+// checked, as the uniform loss.a and loss.scale are not.  Needs Validate(d)
+// only, so cse_create refuses these before it touches a device;
+// ValidateGroups applies it too.  opts may be null (no options to check).
+int ValidateLossData(const cse_problem_desc* d, const cse_options* opts);
+int ValidateGroups(const cse_problem_desc* d, UserLookup lookup, ProgramPlan* P,
+                   const cse_options* opts = nullptr);
 
 // Plans group gi: G and T are overwritten, P's sums advance.
 void PlanGroup(const cse_problem_desc* d, const cse_options& opts, int gi, ProgramPlan* P,

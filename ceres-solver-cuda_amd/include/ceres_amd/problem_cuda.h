@@ -23,9 +23,20 @@
 //    evaluator uses, cuda_evaluator_kernel.h:355-371), recomputed from the
 //    current state on every Evaluate;
 //  * loss objects are small value types, owned by the problem.
+//
+// Loss objects per residual block: the reference keeps one loss object per
+// block; here blocks are grouped, by default one group per distinct loss
+// *value*.  EvaluatorCUDA::Options::merge_loss_parameters groups the
+// library's losses (Huber, Cauchy, scaled trivial, ScaledLossCUDA of them) on
+// the library's functor kinds by loss *type* instead, each block's (a, scale)
+// travelling in its functor_data row (cse_residual_group.loss_data_size).
+// Out of scope still: a LossFunctionCUDABase / CostFunction class hierarchy,
+// and per-block *user* loss objects (a user loss or a user functor kind keeps
+// one group per distinct loss value).
 #ifndef CERES_AMD_PROBLEM_CUDA_H_
 #define CERES_AMD_PROBLEM_CUDA_H_
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -460,6 +471,13 @@ class EvaluatorCUDA {
     // Let the library build the plus-Jacobians it knows (Manifold::DeviceKind)
     // instead of uploading them every evaluation.
     bool device_manifolds = true;
+    // One group per (functor kind, loss type) -- (kind, loss kind, scaled) --
+    // for the library's losses on the library's kinds, with per-block loss
+    // parameters where the blocks of a group differ in (a, scale); blocks of
+    // a user loss or a user kind are grouped by loss value as before.  Default
+    // false: one group per distinct loss value.  The Python package's
+    // ProblemCUDA.program(merge_loss_parameters=...) groups by the same key.
+    bool merge_loss_parameters = false;
   };
 
   EvaluatorCUDA(ProblemCUDA& problem, const Options& options) : problem_(problem) {
@@ -509,6 +527,14 @@ class EvaluatorCUDA {
   }
 
   cse_evaluator* handle() { return ev_; }
+
+  // Residual groups of the evaluator (cse_info.num_groups): kernel launches
+  // per evaluation.
+  int NumGroups() const {
+    cse_info info{};
+    Check(cse_get_info(ev_, &info), "cse_get_info");
+    return (int)info.num_groups;
+  }
 
  private:
   static void Check(int rc, const char* what) {
@@ -610,24 +636,54 @@ class EvaluatorCUDA {
 
     // One group per (functor kind, loss): the per-type evaluator registry
     // (problem_cuda.h:462-468, registered_cuda_evaluators.cc:294-298).
+    // With merge_loss_parameters, one group per (functor kind, loss type) for
+    // library losses on library kinds (by_type; a, scale and the user bytes
+    // leave the key), each block's (a, scale) kept beside its data.
     using UserBytes = std::array<double, CSE_USER_LOSS_BYTES / 8>;
-    std::map<std::tuple<int, int, double, int, double, UserBytes>, GroupStorage> groups;
+    std::map<std::tuple<bool, int, int, double, int, double, UserBytes>, GroupStorage> groups;
     for (int64_t i = 0; i < nrb; ++i) {
       const auto& R = problem_.residuals_[program_residuals_[i]];
-      UserBytes ub;
-      std::memcpy(ub.data(), R.loss.user, sizeof(ub));
-      auto key = std::make_tuple((int)R.kind, R.loss.kind, R.loss.a, R.loss.scaled, R.loss.scale, ub);
+      const bool by_type = o.merge_loss_parameters && R.loss.kind != CSE_LOSS_USER &&
+                           (int)R.kind < CSE_FUNCTOR_USER_FIRST &&
+                           (R.loss.kind != CSE_LOSS_TRIVIAL || R.loss.scaled);
+      UserBytes ub{};
+      if (!by_type) std::memcpy(ub.data(), R.loss.user, sizeof(ub));
+      auto key = std::make_tuple(by_type, (int)R.kind, R.loss.kind, by_type ? 0.0 : R.loss.a,
+                                 R.loss.scaled, by_type ? 0.0 : R.loss.scale, ub);
       GroupStorage& g = groups[key];
       g.g.functor_kind = R.kind;
       g.g.loss = R.loss;
       g.index.push_back(i);
       for (int b : R.blocks) g.ids.push_back(program_index[b]);
       g.data.insert(g.data.end(), R.data.begin(), R.data.end());
+      if (by_type) {
+        g.loss_data.push_back(R.loss.a);
+        g.loss_data.push_back(R.loss.scaled ? R.loss.scale : 1.0);
+      }
     }
     for (auto& kv : groups) group_storage_.push_back(std::move(kv.second));
     std::vector<cse_residual_group> gs;
     for (auto& g : group_storage_) {
-      g.g.reserved = 0;
+      g.g.loss_data_size = 0;
+      const size_t n = g.index.size();
+      bool varies = false;
+      // (only the columns the loss type reads: a for Huber and Cauchy, scale when scaled)
+      const bool reads[2] = {g.g.loss.kind != CSE_LOSS_TRIVIAL, g.g.loss.scaled != 0};
+      for (size_t q = 2; q < g.loss_data.size(); ++q)
+        varies = varies || (reads[q & 1] && g.loss_data[q] != g.loss_data[q & 1]);
+      if (varies) {
+        // Rows widened by the block's (a, scale); all-equal groups stay
+        // uniform (g.g.loss is the first block's, equal to every other's).
+        const size_t D = g.data.size() / n;
+        std::vector<double> rows(n * (D + 2));
+        for (size_t q = 0; q < n; ++q) {
+          std::copy(g.data.begin() + q * D, g.data.begin() + (q + 1) * D, rows.begin() + q * (D + 2));
+          rows[q * (D + 2) + D] = g.loss_data[2 * q];
+          rows[q * (D + 2) + D + 1] = g.loss_data[2 * q + 1];
+        }
+        g.data.swap(rows);
+        g.g.loss_data_size = 2;
+      }
       g.g.num_blocks = (int64_t)g.index.size();
       g.g.residual_block_index = g.index.data();
       g.g.first_residual_block = 0;
@@ -678,6 +734,7 @@ class EvaluatorCUDA {
     std::vector<int64_t> index;
     std::vector<int32_t> ids;
     std::vector<double> data;
+    std::vector<double> loss_data;  // [n][2] (a, scale): groups merged by loss type
   };
   ProblemCUDA& problem_;
   cse_evaluator* ev_ = nullptr;

@@ -33,8 +33,10 @@ extern "C" {
  * 4: user functor kinds (cse_register_functor, cse_functor_shape),
  *    CSE_LOSS_USER and cse_loss.user, cse_schur_init_gradient.
  * 5: cse_functor_ops.fused_points / camera_gradient (the fused gradient for
- *    user kinds) and camera_gradient_args_size (was reserved[0]). */
-#define CSE_ABI_VERSION 5
+ *    user kinds) and camera_gradient_args_size (was reserved[0]).
+ * 6: cse_residual_group.loss_data_size (was `reserved`, 0 in every
+ *    descriptor): per-block loss parameters in the functor_data rows. */
+#define CSE_ABI_VERSION 6
 
 /* Return codes. */
 #define CSE_OK 0
@@ -148,12 +150,33 @@ typedef enum cse_manifold_kind {
 /* All residual blocks of one (functor kind, loss) type; replaces one
  * AutoDiffResidualBlockCUDAEvaluator<F, Loss, kR, Ns...> and its residual
  * blocks (include/ceres/internal/autodiff_residual_block_cuda_evaluator.h:62-334,
- * registered per std::type_index in problem_cuda.h:462-468).  The loss is
- * uniform over the group (one loss object per type is what ProblemCUDA
- * users register in practice; groups may be split to vary it). */
+ * registered per std::type_index in problem_cuda.h:462-468).
+ *
+ * The loss *type* (loss.kind, loss.scaled) is uniform over the group.  Its
+ * parameters are either uniform too (loss_data_size 0: loss.a and loss.scale
+ * hold for every block) or per block (loss_data_size 2), as the reference
+ * keeps one loss object per residual block
+ * (autodiff_residual_block_cuda_evaluator.h:100-132): every functor_data row
+ * then ends with the block's own (a, scale) -- per-observation weights
+ * (ScaledLossCUDA(rho, w_i)) or per-block Huber/Cauchy widths in one group,
+ * one launch, with the fused gradient and the Schur operators a single group
+ * gets.  Per-block parameters are for the library's Huber, Cauchy and
+ * (scaled) trivial losses on the library's functor kinds with
+ * cse_options.jacobian_form = CSE_JACOBIAN_CLOSED_FORM; cse_create refuses
+ * them (CSE_ERR_UNSUPPORTED) with CSE_LOSS_USER, with user functor kinds
+ * (>= CSE_FUNCTOR_USER_FIRST: their launch tables are fixed-size and have no
+ * per-block slots, and a user loss object per block has no place in a row;
+ * such groups are still split by loss value), with the TEST_* kinds and with
+ * CSE_JACOBIAN_JET, and (CSE_ERR_INVALID) the unscaled trivial loss, where
+ * nothing varies. */
 typedef struct cse_residual_group {
   int32_t functor_kind;               /* cse_functor_kind */
-  int32_t reserved;
+  /* Trailing loss doubles of each functor_data row: 0 = none (the loss
+   * parameters are loss.a, loss.scale), 2 = the block's (a, scale); loss.a
+   * and loss.scale are then ignored, and the scale column too when
+   * loss.scaled == 0.  Any other value: CSE_ERR_INVALID.  (ABI <= 5:
+   * `reserved`, 0.) */
+  int32_t loss_data_size;
   cse_loss loss;
   int64_t num_blocks;
   /* Global residual block index (program order, ResidualBlock::index())
@@ -162,7 +185,8 @@ typedef struct cse_residual_group {
   int64_t first_residual_block;
   /* [num_blocks][num parameter blocks of the kind], program indices. */
   const int32_t* parameter_block_ids;
-  /* [num_blocks][data size of the kind] functor constants. */
+  /* [num_blocks][data size of the kind + loss_data_size]: the functor
+   * constants, then the block's loss parameters. */
   const double* functor_data;
 } cse_residual_group;
 
