@@ -7,7 +7,9 @@ whose every evaluation is the HIP evaluator and whose linear solve is a
 preconditioned CG on the device's implicit Schur complement
 (--linear_solver iterative_schur, the reference benchmark's solver, with its
 jacobi / schur_jacobi / identity preconditioners) or on the normal equations
-(--linear_solver cgnr); no Jacobian value leaves HBM.  Prints a FullReport-style table of the evaluator timers
+(--linear_solver cgnr), or -- DENSE_SCHUR, for up to a few hundred cameras --
+the explicit dense Schur complement formed on the device and its Cholesky
+factorization (--linear_solver dense_schur); no Jacobian value leaves HBM.  Prints a FullReport-style table of the evaluator timers
 (solver.cc: "Residual only evaluation", "Jacobian & residual evaluation",
 "Linear solver", "Plus").
 
@@ -53,10 +55,13 @@ def parse(argv=None):
     ap.add_argument("--max_linear_solver_iterations", type=int, default=500)
     ap.add_argument("--eta", type=float, default=1e-2, help="CG forcing tolerance")
     ap.add_argument("--initial_trust_region_radius", type=float, default=1e4)
-    ap.add_argument("--linear_solver", default="iterative_schur", choices=["iterative_schur", "cgnr"],
+    ap.add_argument("--linear_solver", default="iterative_schur", choices=["iterative_schur", "cgnr", "dense_schur"],
                     help="iterative_schur (the reference benchmark's, README.md:143-184): PCG on "
                          "the implicit Schur complement (cse_schur_*); cgnr: PCG on the normal "
-                         "equations (cse_cgnr_multiply)")
+                         "equations (cse_cgnr_multiply); dense_schur: the dense reduced camera "
+                         "matrix (cse_schur_complement) and its Cholesky factorization")
+    ap.add_argument("--max_schur_gb", type=float, default=16.0,
+                    help="dense_schur: refuse when the plan and the dense S together take more")
     ap.add_argument("--preconditioner", default="jacobi",
                     choices=["identity", "jacobi", "schur_jacobi"],
                     help="iterative_schur's preconditioner (bundle_adjuster.cc default: jacobi)")
@@ -76,6 +81,22 @@ class Timers:
         for name, (tot, n) in self.t.items():
             lines.append(f"  {name:<34s}{tot:12.6f} ({n})")
         return "\n".join(lines)
+
+
+def cholesky_solve(S, rhs):
+    """x with S x = rhs for the symmetric positive definite device matrix S
+    (DenseSchurComplementSolver::SolveReducedLinearSystem's LLT), on the device;
+    on the host with numpy where torch's device factorization is not available."""
+    import torch
+    try:
+        L, info = torch.linalg.cholesky_ex(S)
+        if int(info.item()) != 0:
+            raise SystemExit(f"dense_schur: S is not positive definite (leading minor {int(info.item())})")
+        return torch.cholesky_solve(rhs.unsqueeze(1), L).squeeze(1).contiguous()
+    except RuntimeError:
+        c = np.linalg.cholesky(S.cpu().numpy())
+        y = np.linalg.solve(c, rhs.cpu().numpy())
+        return torch.from_numpy(np.linalg.solve(c.T, y)).to(S.device)
 
 
 def solve(args):
@@ -98,8 +119,8 @@ def solve(args):
     if args.use_quaternions:
         cams = bal.to_quaternion_cameras(cams)
     manifold = args.use_quaternions and args.use_manifolds
-    if args.use_quaternions and not manifold and args.linear_solver == "iterative_schur":
-        raise SystemExit("iterative_schur takes 9-column cameras: add --use_manifolds or use cgnr")
+    if args.use_quaternions and not manifold and args.linear_solver != "cgnr":
+        raise SystemExit(f"{args.linear_solver} takes 9-column cameras: add --use_manifolds or use cgnr")
     prog = bal.program(cams, pts, ci[order], pi[order], obs[order], loss=loss, format=args.format,
                        quaternion_manifold=manifold)
     timers.add("Preprocessor", time.perf_counter() - t0)
@@ -123,9 +144,9 @@ def solve(args):
         timers.add(name, time.perf_counter() - s)
         return out
 
-    # ITERATIVE_SCHUR takes g = J^T r from its own init (cse_schur_init_gradient,
+    # The Schur solvers take g = J^T r from their own init (cse_schur_init_gradient,
     # every solve, before g is read); CGNR from the evaluation.
-    grad_from_init = args.linear_solver == "iterative_schur"
+    grad_from_init = args.linear_solver != "cgnr"
 
     def jacobian_eval(new_point=True):
         # After an accepted step x holds the candidate just evaluated:
@@ -170,12 +191,20 @@ def solve(args):
             rz = rz_new
         return dx, it
 
-    if args.linear_solver == "iterative_schur":
+    if args.linear_solver != "cgnr":
         e_cols, f_cols = ev.schur_structure()
         pre = {"identity": ca._cse.SCHUR_IDENTITY, "jacobi": ca._cse.SCHUR_JACOBI,
                "schur_jacobi": ca._cse.SCHUR_SCHUR_JACOBI}[args.preconditioner]
         rhs = torch.empty(f_cols, dtype=f64, device=dev)
         neg_r = torch.empty(m, dtype=f64, device=dev)
+    if args.linear_solver == "dense_schur":
+        _, _, plan_bytes = ev.schur_complement_plan()
+        need = plan_bytes + 8 * f_cols * f_cols
+        if need > args.max_schur_gb * 2 ** 30:
+            raise SystemExit(f"dense_schur: the plan and the {f_cols} x {f_cols} S take "
+                             f"{need / 2 ** 30:.2f} GiB, above --max_schur_gb {args.max_schur_gb:g}; "
+                             "use iterative_schur")
+        S = torch.empty((f_cols, f_cols), dtype=f64, device=dev)
 
     def schur_solve(lam):
         # IterativeSchurComplementSolver (iterative_schur_complement_solver.cc:
@@ -210,6 +239,20 @@ def solve(args):
         ev.schur_back_substitute_device(xf.data_ptr(), dx.data_ptr())
         return dx, it
 
+    def dense_schur_solve(lam):
+        # DenseSchurComplementSolver (schur_complement_solver.cc): the same
+        # augmented system reduced to the dense S by SchurEliminator::Eliminate
+        # (cse_schur_complement), S dx_f = rhs by Cholesky, back substitution.
+        torch.neg(r, out=neg_r)
+        sqrt_lam_d = torch.sqrt(lam * D)
+        ev.schur_init_gradient_device(jac.data_ptr(), sqrt_lam_d.data_ptr(), neg_r.data_ptr(),
+                                      rhs.data_ptr(), g.data_ptr(), ca._cse.SCHUR_IDENTITY)
+        ev.schur_complement_device(S.data_ptr())
+        xf = cholesky_solve(S, rhs)
+        dx = torch.empty(n, dtype=f64, device=dev)
+        ev.schur_back_substitute_device(xf.data_ptr(), dx.data_ptr())
+        return dx, 0
+
     status = timed("Jacobian & residual evaluation", jacobian_eval)
     if status != 0:
         raise SystemExit("initial evaluation failed")
@@ -237,7 +280,8 @@ def solve(args):
             ev.left_multiply_device(jac2.data_ptr(), ones.data_ptr(), D.data_ptr())
             D.clamp_(min=1e-6)
             d_stale = False
-        solver = schur_solve if args.linear_solver == "iterative_schur" else cgnr
+        solver = {"iterative_schur": schur_solve, "dense_schur": dense_schur_solve,
+                  "cgnr": cgnr}[args.linear_solver]
         dx, cg_iters = timed("Linear solver", lambda: solver(1.0 / radius))
         timed("Plus", lambda: ev.plus_device(x.data_ptr(), dx.data_ptr(), cand.data_ptr()))
 

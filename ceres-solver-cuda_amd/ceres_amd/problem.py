@@ -716,6 +716,27 @@ class Evaluator:
         return _cse.check(_cse.lib().cse_schur_back_substitute(self.handle, d_x, d_y),
                           "cse_schur_back_substitute")
 
+    def schur_complement_device(self, d_S, ld=None):
+        """The dense reduced camera matrix S (SchurEliminator::Eliminate's lhs,
+        for DENSE_SCHUR) into row-major d_S (num_cols_f rows of ld >= num_cols_f
+        doubles; ld defaults to num_cols_f), both triangles; needs a
+        schur_init*_device on this evaluator (cse_schur_complement)."""
+        if ld is None:
+            ld = self.schur_structure()[1]
+        return _cse.check(_cse.lib().cse_schur_complement(self.handle, d_S, int(ld)),
+                          "cse_schur_complement")
+
+    def schur_complement_plan(self):
+        """(num_blocks, num_pairs, plan_bytes) of schur_complement_device's
+        co-visibility plan: the non-zero 9 x 9 blocks of S's upper triangle,
+        the residual-block pairs summed into them and the device bytes the
+        plan takes.  Allocates nothing on the device."""
+        nb, npair, nbytes = C.c_int64(), C.c_int64(), C.c_int64()
+        _cse.check(_cse.lib().cse_schur_complement_plan(self.handle, C.byref(nb), C.byref(npair),
+                                                        C.byref(nbytes)),
+                   "cse_schur_complement_plan")
+        return nb.value, npair.value, nbytes.value
+
     def plus_device(self, d_state, d_delta, d_out):
         """Device-pointer Plus on the evaluator's stream.  Async."""
         return _cse.check(_cse.lib().cse_plus_device(self.handle, d_state, d_delta, d_out),

@@ -34,6 +34,7 @@
 #include "per_block_loss_kernels.h"
 #include "plan.hpp"
 #include "schur_kernels.hpp"
+#include "schur_complement_kernels.hpp"
 
 namespace cse {
 std::string& LastError();  // layout.cpp: one per thread (cse_last_error reads it here)
@@ -305,6 +306,15 @@ struct cse_evaluator {
     bool ready = false;
     int preconditioner = CSE_SCHUR_IDENTITY;
     const double *jac = nullptr, *D = nullptr, *b = nullptr;
+    // The explicit complement's pair plan (cse::PlanSchurPairs): counted on
+    // the first plan query, built and uploaded on the first
+    // cse_schur_complement; structure only, so it outlives every init.
+    struct Pairs : cse::SchurPairCounts {
+      bool counted = false, uploaded = false;
+      DevBuf<int32_t> block_row, block_col, chunk_block, pairs;
+      DevBuf<int64_t> pair_begin, chunk_off;
+      DevBuf<double> partial;
+    } pairs;
   } schur;
 };
 
@@ -1369,6 +1379,111 @@ int cse_schur_back_substitute(cse_evaluator* ev, const double* d_x, double* d_y)
   LaunchSchurPass<cse::kSchurBack>(MakeSchurArgs(ev, d_x, d_y), s);
   CSE_HIP(hipGetLastError());
   CSE_HIP(hipMemcpyAsync(d_y + S.e_cols, d_x, S.f_cols * sizeof(double), hipMemcpyDeviceToDevice, s));
+  return CSE_OK;
+}
+
+extern "C++" {
+namespace {
+// The pair plan of the explicit complement, from the group's ids as they were
+// uploaded (the descriptor is gone after cse_create).
+int SchurPairPlanOf(cse_evaluator* ev, bool upload) {
+  auto& Q = ev->schur.pairs;
+  if (upload ? Q.uploaded : Q.counted) return CSE_OK;
+  const Group& G = ev->groups[0];
+  std::vector<int32_t> ids((size_t)(2 * G.n));
+  CSE_HIP(hipStreamSynchronize(ev->stream));
+  if (G.n > 0) CSE_HIP(hipMemcpy(ids.data(), G.ids.p, ids.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  cse::SchurPairPlan P;
+  int rc = cse::PlanSchurPairs(ids.data(), G.n, !upload, &P);
+  if (rc) return rc;
+  static_cast<cse::SchurPairCounts&>(Q) = P;
+  Q.counted = true;
+  if (!upload) return CSE_OK;
+  hipStream_t s = ev->stream;
+  rc = Q.block_row.upload(P.block_row.data(), P.block_row.size(), s);
+  if (!rc) rc = Q.block_col.upload(P.block_col.data(), P.block_col.size(), s);
+  if (!rc) rc = Q.pair_begin.upload(P.pair_begin.data(), P.pair_begin.size(), s);
+  if (!rc) rc = Q.chunk_off.upload(P.chunk_off.data(), P.chunk_off.size(), s);
+  if (!rc) rc = Q.chunk_block.upload(P.chunk_block.data(), P.chunk_block.size(), s);
+  if (!rc) rc = Q.pairs.upload(P.pairs.data(), P.pairs.size(), s);
+  if (!rc) rc = Q.partial.alloc((size_t)(P.num_chunks * cse::kSchurBlockDoubles));
+  // The copies read P's tables: wait before P goes out of scope.
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = Fail(CSE_ERR_HIP, "plan upload failed");
+  if (rc) {
+    for (DevBuf<int32_t>* b : {&Q.block_row, &Q.block_col, &Q.chunk_block, &Q.pairs}) b->release();
+    Q.pair_begin.release();
+    Q.chunk_off.release();
+    Q.partial.release();
+    return rc;
+  }
+  Q.uploaded = true;
+  return CSE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int cse_schur_complement_plan(cse_evaluator* ev, int64_t* num_blocks, int64_t* num_pairs,
+                              int64_t* plan_bytes) {
+  int rc = SchurCheck(ev, false);
+  if (rc) return rc;
+  if ((rc = SchurPairPlanOf(ev, false))) return rc;
+  const auto& Q = ev->schur.pairs;
+  if (num_blocks) *num_blocks = Q.num_blocks;
+  if (num_pairs) *num_pairs = Q.num_pairs;
+  if (plan_bytes) *plan_bytes = Q.plan_bytes;
+  return CSE_OK;
+}
+
+int cse_schur_complement(cse_evaluator* ev, double* d_S, int64_t ld) {
+  int rc = SchurCheck(ev, true);
+  if (rc) return rc;
+  auto& S = ev->schur;
+  if (!d_S) return Fail(CSE_ERR_INVALID, "null pointer");
+  if (ld < S.f_cols) return Fail(CSE_ERR_INVALID, "cse_schur_complement: ld is smaller than num_cols_f");
+  if ((rc = SchurPairPlanOf(ev, true))) return rc;
+  const Group& G = ev->groups[0];
+  const auto& Q = S.pairs;
+  hipStream_t s = ev->stream;
+  // Blocks of cameras that share no point stay zero; the rows' padding
+  // [f_cols, ld) is not touched.
+  if (S.f_cols > 0)
+    CSE_HIP(hipMemset2DAsync(d_S, (size_t)ld * sizeof(double), 0, (size_t)S.f_cols * sizeof(double),
+                             (size_t)S.f_cols, s));
+  if (S.D && S.f_cols > 0)
+    hipLaunchKernelGGL(cse::SchurDiagonalFillKernel,
+                       dim3((unsigned)((S.f_cols + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                       dim3(cse::kBlockThreads), 0, s, S.D, S.e_cols, d_S, ld, S.f_cols);
+  cse::SchurPairArgs a{};
+  a.ids = G.ids.p;
+  a.jac = S.jac;
+  a.f_base = G.jac_base[0][0];
+  a.e_base = G.jac_base[1][0];
+  a.f_col_base = S.f_col_base;
+  a.e_col_base = G.delta_base[1];
+  a.e_cols = S.e_cols;
+  a.D = S.D;
+  a.ete_inv = S.ete_inv.p;
+  a.block_row = Q.block_row.p;
+  a.block_col = Q.block_col.p;
+  a.pair_begin = Q.pair_begin.p;
+  a.chunk_off = Q.chunk_off.p;
+  a.chunk_block = Q.chunk_block.p;
+  a.pairs = Q.pairs.p;
+  a.nblocks = Q.num_blocks;
+  a.nchunks = Q.num_chunks;
+  a.partial = Q.partial.p;
+  a.S = d_S;
+  a.ld = ld;
+  if (Q.num_chunks > 0) {
+    hipLaunchKernelGGL((cse::SchurPairChunkKernel<9>),
+                       dim3((unsigned)((Q.num_chunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
+                       dim3(cse::kBlockThreads), 0, s, a);
+    const int64_t entries = Q.num_blocks * cse::kSchurBlockDoubles;
+    hipLaunchKernelGGL((cse::SchurPairFinishKernel<9>),
+                       dim3((unsigned)((entries + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                       dim3(cse::kBlockThreads), 0, s, a);
+  }
+  CSE_HIP(hipGetLastError());
   return CSE_OK;
 }
 

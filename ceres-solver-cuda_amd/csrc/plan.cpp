@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <new>
 #include <utility>
 
 namespace cse {
@@ -912,6 +913,76 @@ void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* 
       P->pbs[b] = {pb.state_offset, pb.delta_offset, pj, pb.tangent_size, pb.is_constant};
     }
   }
+}
+
+int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPlan* plan) {
+  *plan = SchurPairPlan{};
+  if (n >= ((int64_t)1 << 31))
+    return CseFail(CSE_ERR_UNSUPPORTED, "Schur complement plan: 2^31 or more residual blocks");
+  try {
+    if (!counts_only) {
+      plan->pair_begin.assign(1, 0);
+      plan->chunk_off.assign(1, 0);
+    }
+    if (n <= 0) return CSE_OK;
+    int32_t cmin = ids[0], cmax = ids[0];
+    for (int64_t i = 1; i < n; ++i) {
+      cmin = std::min(cmin, ids[2 * i]);
+      cmax = std::max(cmax, ids[2 * i]);
+    }
+    const int64_t C = (int64_t)cmax - cmin + 1;
+    // Pass 1: pairs per block, in a dense C x C table (upper triangle used).
+    std::vector<int64_t> at((size_t)(C * C), 0);
+    auto each_pair = [&](auto&& f) {
+      int64_t r0 = 0;
+      for (int64_t i = 1; i <= n; ++i) {
+        if (i < n && ids[2 * i + 1] == ids[2 * r0 + 1]) continue;
+        for (int64_t b = r0; b < i; ++b) {
+          const int64_t c = ids[2 * b] - cmin;
+          for (int64_t b2 = r0; b2 < i; ++b2) {
+            const int64_t c2 = ids[2 * b2] - cmin;
+            if (c <= c2) f(c * C + c2, b, b2);
+          }
+        }
+        r0 = i;
+      }
+    };
+    each_pair([&](int64_t cell, int64_t, int64_t) { ++at[(size_t)cell]; });
+    // The blocks in lexicographic order; each cell becomes its block's cursor.
+    for (int64_t c = 0; c < C; ++c) {
+      for (int64_t c2 = c; c2 < C; ++c2) {
+        int64_t& cell = at[(size_t)(c * C + c2)];
+        if (cell == 0) continue;
+        const int64_t count = cell, chunks = (count + kSchurPairChunk - 1) / kSchurPairChunk;
+        cell = plan->num_pairs;
+        if (!counts_only) {
+          plan->block_row.push_back((int32_t)(cmin + c));
+          plan->block_col.push_back((int32_t)(cmin + c2));
+          plan->pair_begin.push_back(plan->num_pairs + count);
+          plan->chunk_off.push_back(plan->num_chunks + chunks);
+          plan->chunk_block.insert(plan->chunk_block.end(), (size_t)chunks, (int32_t)plan->num_blocks);
+        }
+        plan->num_blocks += 1;
+        plan->num_pairs += count;
+        plan->num_chunks += chunks;
+      }
+    }
+    plan->plan_bytes = 2 * 4 * plan->num_blocks + 2 * 8 * (plan->num_blocks + 1) + 4 * plan->num_chunks +
+                       2 * 4 * plan->num_pairs + 8LL * kSchurBlockDoubles * plan->num_chunks;
+    if (counts_only) return CSE_OK;
+    // Pass 2: the runs again in the same order, so a block's pairs come out
+    // ordered by (e block, b, b').
+    plan->pairs.resize((size_t)(2 * plan->num_pairs));
+    each_pair([&](int64_t cell, int64_t b, int64_t b2) {
+      const int64_t k = at[(size_t)cell]++;
+      plan->pairs[(size_t)(2 * k)] = (int32_t)b;
+      plan->pairs[(size_t)(2 * k + 1)] = (int32_t)b2;
+    });
+  } catch (const std::bad_alloc&) {
+    *plan = SchurPairPlan{};
+    return CseFail(CSE_ERR_OOM, "Schur complement plan: host allocation failed");
+  }
+  return CSE_OK;
 }
 
 }  // namespace cse

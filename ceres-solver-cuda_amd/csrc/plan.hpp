@@ -256,6 +256,41 @@ void PlanGroup(const cse_problem_desc* d, const cse_options& opts, int gi, Progr
 // (only = the plan of the program's one group, null when it has several).
 void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* P);
 
+// ---- The explicit Schur complement's pair plan (cse_schur_complement): which
+// residual-block pairs add into which 9 x 9 block of S.  Host only; built on
+// the first cse_schur_complement or cse_schur_complement_plan call, never by
+// cse_create (it is sum_p k_p^2 in size).
+constexpr int kSchurPairChunk = 64;  // pairs per work chunk (one wave each)
+constexpr int kSchurBlockDoubles = 81;
+
+struct SchurPairCounts {
+  int64_t num_blocks = 0;  // non-zero blocks of S's upper triangle, diagonal included
+  int64_t num_pairs = 0;   // pair records
+  int64_t num_chunks = 0;  // work chunks: sum over blocks of ceil(pairs / kSchurPairChunk)
+  int64_t plan_bytes = 0;  // device bytes of the tables below and the chunk partials
+};
+struct SchurPairPlan : SchurPairCounts {
+  // Block k = S(block_row[k], block_col[k]), parameter-block ids with row <=
+  // col, in lexicographic order; its pairs are [pair_begin[k], pair_begin[k+1])
+  // and its chunks [chunk_off[k], chunk_off[k+1]): chunk q of block k takes
+  // kSchurPairChunk pairs from pair_begin[k] + (q - chunk_off[k]) kSchurPairChunk,
+  // so no chunk straddles a block.
+  std::vector<int32_t> block_row, block_col;
+  std::vector<int64_t> pair_begin, chunk_off;  // [num_blocks + 1]
+  std::vector<int32_t> chunk_block;            // [num_chunks]
+  // [num_pairs][2]: residual blocks (b, b') of one e block with f block of b =
+  // block_row, of b' = block_col, ordered by (e block, b, b') inside a block.
+  // A diagonal block holds every ordered pair, b = b' included (that pair
+  // also carries F_b^T F_b).
+  std::vector<int32_t> pairs;
+};
+// ids: the group's [n][2] (f block, e block), sorted by e block (each e
+// block's rows one contiguous run).  counts_only fills the SchurPairCounts
+// part alone.  Needs a host table of 8 C^2 bytes for C = the f-block id range
+// (1/81 of the dense S the plan is for).  CSE_ERR_UNSUPPORTED when n >= 2^31
+// (pair entries are int32), CSE_ERR_OOM when host memory runs out.
+int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPlan* plan);
+
 }  // namespace cse
 
 #endif  // CSE_PLAN_HPP_

@@ -499,6 +499,25 @@ int cse_schur_precondition(cse_evaluator* ev, const double* d_x, double* d_y);
  * (num_effective_parameters) = [(E^T E + D_e^2)^-1 E^T (b - F x); x]. */
 int cse_schur_back_substitute(cse_evaluator* ev, const double* d_x, double* d_y);
 
+/* SchurEliminator::Eliminate's lhs (schur_eliminator_impl.h) into a dense
+ * BlockRandomAccessDenseMatrix-like buffer, for DENSE_SCHUR
+ * (schur_complement_solver.cc).  Needs cse_schur_init (any preconditioner) on
+ * this evaluator: uses the Jacobian, D and M_p it bound/computed.  Assigns all
+ * f_cols x f_cols entries of row-major d_S with leading dimension ld >= f_cols
+ * (zeros where two cameras share no point), both triangles; entries
+ * [row][f_cols..ld) are not touched.  Asynchronous on the evaluator's stream,
+ * deterministic.  A point that sees one camera in several residual blocks is
+ * fine (its cross terms land in the diagonal block).  The first call builds
+ * the co-visibility plan on the host and uploads it (CSE_ERR_OOM when it does
+ * not fit); later calls, after any cse_schur_init, reuse it. */
+int cse_schur_complement(cse_evaluator* ev, double* d_S, int64_t ld);
+
+/* Counts only, no allocation: the non-zero 9x9 blocks of S's upper triangle
+ * (co-visible camera pairs, diagonal included), the pair records of the plan
+ * and the device bytes the plan will take; any pointer may be NULL. */
+int cse_schur_complement_plan(cse_evaluator* ev, int64_t* num_blocks,
+                              int64_t* num_pairs, int64_t* plan_bytes);
+
 /* ---- One host solve, several GPUs --------------------------------------
  * The reference evaluates on one device (ContextImpl's single stream,
  * include/ceres/internal/cuda_buffer.h:98) and Ceres' host solve calls one
