@@ -61,11 +61,22 @@ def parse(argv=None):
                          "equations (cse_cgnr_multiply); dense_schur: the dense reduced camera "
                          "matrix (cse_schur_complement) and its Cholesky factorization")
     ap.add_argument("--max_schur_gb", type=float, default=16.0,
-                    help="dense_schur: refuse when the plan and the dense S together take more")
+                    help="dense_schur: refuse when the plan and the dense S together take more; "
+                         "--use_explicit_schur_complement: the plan, the structure and the blocks of S")
+    ap.add_argument("--use_explicit_schur_complement", action="store_true",
+                    help="iterative_schur only (bundle_adjuster.cc's flag, Solver::Options::"
+                         "use_explicit_schur_complement): form the block-sparse S once per linear solve "
+                         "(cse_schur_complement_sparse) and run the PCG on it (cse_schur_explicit_multiply) "
+                         "instead of on the implicit operator.  Not a faster solve on the shapes measured "
+                         "(level at 49 cameras, slower beyond): see DESIGN 3.6b")
     ap.add_argument("--preconditioner", default="jacobi",
                     choices=["identity", "jacobi", "schur_jacobi"],
                     help="iterative_schur's preconditioner (bundle_adjuster.cc default: jacobi)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.use_explicit_schur_complement and args.linear_solver != "iterative_schur":
+        raise SystemExit("--use_explicit_schur_complement needs --linear_solver iterative_schur, not "
+                         f"{args.linear_solver}")
+    return args
 
 
 class Timers:
@@ -205,6 +216,25 @@ def solve(args):
                              f"{need / 2 ** 30:.2f} GiB, above --max_schur_gb {args.max_schur_gb:g}; "
                              "use iterative_schur")
         S = torch.empty((f_cols, f_cols), dtype=f64, device=dev)
+    if args.use_explicit_schur_complement:
+        _, _, plan_bytes = ev.schur_complement_plan()
+        _, num_blocks, structure_bytes = ev.schur_complement_sparse_counts()
+        need = structure_bytes + plan_bytes + 648 * num_blocks
+        if need > args.max_schur_gb * 2 ** 30:
+            raise SystemExit(f"use_explicit_schur_complement: the plan, the structure and the {num_blocks} "
+                             f"blocks of S take {need / 2 ** 30:.2f} GiB, above --max_schur_gb "
+                             f"{args.max_schur_gb:g}; use iterative_schur without the flag")
+        S_values = torch.empty(81 * num_blocks, dtype=f64, device=dev)
+        # SparseSchurComplementSolver::InitStorage: the co-visibility plan and
+        # the block structure, built on the host and uploaded once.
+        t0 = time.perf_counter()
+        ev.schur_complement_sparse_upload()
+        timers.add("Schur complement structure", time.perf_counter() - t0)
+
+        def schur_op(d_x, d_y):
+            ev.schur_explicit_multiply_device(S_values.data_ptr(), d_x, d_y)
+    elif args.linear_solver == "iterative_schur":
+        schur_op = ev.schur_multiply_device
 
     def schur_solve(lam):
         # IterativeSchurComplementSolver (iterative_schur_complement_solver.cc:
@@ -214,6 +244,10 @@ def solve(args):
         sqrt_lam_d = torch.sqrt(lam * D)
         ev.schur_init_gradient_device(jac.data_ptr(), sqrt_lam_d.data_ptr(), neg_r.data_ptr(),
                                       rhs.data_ptr(), g.data_ptr(), pre)
+        if args.use_explicit_schur_complement:
+            # SolveReducedLinearSystemUsingConjugateGradients
+            # (schur_complement_solver.cc): S once, then the PCG on its blocks.
+            ev.schur_complement_sparse_device(S_values.data_ptr())
         xf = torch.zeros(f_cols, dtype=f64, device=dev)
         res = rhs.clone()
         z = torch.zeros_like(res)
@@ -224,7 +258,7 @@ def solve(args):
         bn = rhs.norm()
         it = 0
         for it in range(1, args.max_linear_solver_iterations + 1):
-            ev.schur_multiply_device(p.data_ptr(), Ap.data_ptr())
+            schur_op(p.data_ptr(), Ap.data_ptr())
             alpha = rz / torch.dot(p, Ap)
             xf += alpha * p
             res -= alpha * Ap

@@ -737,6 +737,53 @@ class Evaluator:
                    "cse_schur_complement_plan")
         return nb.value, npair.value, nbytes.value
 
+    def schur_complement_sparse_counts(self):
+        """(num_block_rows, num_blocks, device_bytes) of the block-sparse S:
+        its cameras, the 9 x 9 blocks of its upper triangle (every diagonal
+        block and the co-visible pairs) and the device bytes of its structure
+        tables.  Allocates nothing on the device."""
+        rows, nb, nbytes = C.c_int64(), C.c_int64(), C.c_int64()
+        _cse.check(_cse.lib().cse_schur_complement_sparse_structure(
+            self.handle, C.byref(rows), C.byref(nb), C.byref(nbytes), None, None),
+            "cse_schur_complement_sparse_structure")
+        return rows.value, nb.value, nbytes.value
+
+    def schur_complement_sparse_structure(self):
+        """(row_begin int64[C+1], block_col int32[num_blocks], device_bytes):
+        S's upper triangle as block-compressed rows, BlockRandomAccessSparse-
+        Matrix's cells; camera c's blocks are [row_begin[c], row_begin[c+1]),
+        the diagonal first (cse_schur_complement_sparse_structure).  Builds and
+        uploads the structure."""
+        rows, nb, nbytes = self.schur_complement_sparse_counts()
+        row_begin = np.empty(rows + 1, np.int64)
+        block_col = np.empty(nb, np.int32)
+        _cse.check(_cse.lib().cse_schur_complement_sparse_structure(
+            self.handle, None, None, None, row_begin.ctypes.data_as(_cse.P_i64),
+            block_col.ctypes.data_as(_cse.P_i32)), "cse_schur_complement_sparse_structure")
+        return row_begin, block_col, nbytes
+
+    def schur_complement_sparse_upload(self):
+        """Builds and uploads the block-sparse structure now (the first
+        schur_complement_sparse_device would otherwise), without copying
+        block_col out."""
+        rows = self.schur_complement_sparse_counts()[0]
+        row_begin = np.empty(rows + 1, np.int64)
+        _cse.check(_cse.lib().cse_schur_complement_sparse_structure(
+            self.handle, None, None, None, row_begin.ctypes.data_as(_cse.P_i64), None),
+            "cse_schur_complement_sparse_structure")
+
+    def schur_complement_sparse_device(self, d_values):
+        """The values of the block-sparse S into d_values[num_blocks][9][9], in
+        structure order; needs a schur_init*_device (cse_schur_complement_sparse)."""
+        return _cse.check(_cse.lib().cse_schur_complement_sparse(self.handle, d_values),
+                          "cse_schur_complement_sparse")
+
+    def schur_explicit_multiply_device(self, d_values, d_x, d_y):
+        """d_y = S d_x from schur_complement_sparse_device's values; d_x and
+        d_y may not overlap (cse_schur_explicit_multiply)."""
+        return _cse.check(_cse.lib().cse_schur_explicit_multiply(self.handle, d_values, d_x, d_y),
+                          "cse_schur_explicit_multiply")
+
     def plus_device(self, d_state, d_delta, d_out):
         """Device-pointer Plus on the evaluator's stream.  Async."""
         return _cse.check(_cse.lib().cse_plus_device(self.handle, d_state, d_delta, d_out),

@@ -315,6 +315,18 @@ struct cse_evaluator {
       DevBuf<int64_t> pair_begin, chunk_off;
       DevBuf<double> partial;
     } pairs;
+    // The block-sparse complement's structure (cse::PlanSchurSparse), cached
+    // the same way; row_begin and block_col stay on the host too, for
+    // cse_schur_complement_sparse_structure.
+    struct Sparse : cse::SchurSparseCounts {
+      bool counted = false, uploaded = false;
+      int64_t num_finish = 0;
+      std::vector<int64_t> h_row_begin;
+      std::vector<int32_t> h_block_col;
+      DevBuf<int64_t> row_begin, col_begin;
+      DevBuf<int32_t> block_col, plan_block, sparse_of_plan, finish, col_block;
+      DevBuf<double> contrib;  // [num_blocks][9]: the product's column contributions
+    } sparse;
   } schur;
 };
 
@@ -1386,15 +1398,28 @@ extern "C++" {
 namespace {
 // The pair plan of the explicit complement, from the group's ids as they were
 // uploaded (the descriptor is gone after cse_create).
-int SchurPairPlanOf(cse_evaluator* ev, bool upload) {
+int SchurIds(cse_evaluator* ev, std::vector<int32_t>* ids) {
+  const Group& G = ev->groups[0];
+  ids->resize((size_t)(2 * G.n));
+  CSE_HIP(hipStreamSynchronize(ev->stream));
+  if (G.n > 0) CSE_HIP(hipMemcpy(ids->data(), G.ids.p, ids->size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return CSE_OK;
+}
+
+// keep: receives the host tables of a plan built by this call (the
+// block-sparse structure is made from them); have_ids: the ids, when the
+// caller has downloaded them already.
+int SchurPairPlanOf(cse_evaluator* ev, bool upload, cse::SchurPairPlan* keep = nullptr,
+                    const std::vector<int32_t>* have_ids = nullptr) {
   auto& Q = ev->schur.pairs;
   if (upload ? Q.uploaded : Q.counted) return CSE_OK;
   const Group& G = ev->groups[0];
-  std::vector<int32_t> ids((size_t)(2 * G.n));
-  CSE_HIP(hipStreamSynchronize(ev->stream));
-  if (G.n > 0) CSE_HIP(hipMemcpy(ids.data(), G.ids.p, ids.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  std::vector<int32_t> own;
+  int rc = have_ids ? CSE_OK : SchurIds(ev, &own);
+  if (rc) return rc;
+  const std::vector<int32_t>& ids = have_ids ? *have_ids : own;
   cse::SchurPairPlan P;
-  int rc = cse::PlanSchurPairs(ids.data(), G.n, !upload, &P);
+  rc = cse::PlanSchurPairs(ids.data(), G.n, !upload, &P);
   if (rc) return rc;
   static_cast<cse::SchurPairCounts&>(Q) = P;
   Q.counted = true;
@@ -1417,6 +1442,7 @@ int SchurPairPlanOf(cse_evaluator* ev, bool upload) {
     return rc;
   }
   Q.uploaded = true;
+  if (keep) *keep = std::move(P);  // the host tables, for the block-sparse structure
   return CSE_OK;
 }
 }  // namespace
@@ -1434,25 +1460,75 @@ int cse_schur_complement_plan(cse_evaluator* ev, int64_t* num_blocks, int64_t* n
   return CSE_OK;
 }
 
-int cse_schur_complement(cse_evaluator* ev, double* d_S, int64_t ld) {
-  int rc = SchurCheck(ev, true);
+extern "C++" {
+namespace {
+// The block-sparse structure over the pair plan (both built and uploaded when
+// upload; counts alone otherwise).
+int SchurSparsePlanOf(cse_evaluator* ev, bool upload) {
+  auto& Z = ev->schur.sparse;
+  if (upload ? Z.uploaded : Z.counted) return CSE_OK;
+  const Group& G = ev->groups[0];
+  std::vector<int32_t> ids;
+  int rc = SchurIds(ev, &ids);
   if (rc) return rc;
-  auto& S = ev->schur;
-  if (!d_S) return Fail(CSE_ERR_INVALID, "null pointer");
-  if (ld < S.f_cols) return Fail(CSE_ERR_INVALID, "cse_schur_complement: ld is smaller than num_cols_f");
-  if ((rc = SchurPairPlanOf(ev, true))) return rc;
+  cse::SchurPairPlan P;
+  if ((rc = SchurPairPlanOf(ev, upload, &P, &ids))) return rc;
+  // f index of f block id = f_col_base + 9 id, and camera 0 is f index 0.
+  const int32_t first_id = (int32_t)(-ev->schur.f_col_base / 9);
+  const int64_t C = ev->schur.f_cols / 9;
+  if (upload && P.pair_begin.empty()) {
+    // An earlier call uploaded the pair plan: the block-level tables that the
+    // structure is made from come back from the device.
+    const auto& Q = ev->schur.pairs;
+    try {
+      P.block_row.resize((size_t)Q.num_blocks);
+      P.block_col.resize((size_t)Q.num_blocks);
+      P.chunk_off.resize((size_t)Q.num_blocks + 1);
+    } catch (const std::bad_alloc&) {
+      return Fail(CSE_ERR_OOM, "block-sparse Schur complement: host allocation failed");
+    }
+    if (Q.num_blocks > 0) {
+      CSE_HIP(hipMemcpy(P.block_row.data(), Q.block_row.p, P.block_row.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+      CSE_HIP(hipMemcpy(P.block_col.data(), Q.block_col.p, P.block_col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    CSE_HIP(hipMemcpy(P.chunk_off.data(), Q.chunk_off.p, P.chunk_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  }
+  static_cast<cse::SchurPairCounts&>(P) = ev->schur.pairs;
+  cse::SchurSparsePlan Y;
+  if ((rc = cse::PlanSchurSparse(ids.data(), G.n, P, first_id, C, !upload, &Y))) return rc;
+  static_cast<cse::SchurSparseCounts&>(Z) = Y;
+  Z.counted = true;
+  if (!upload) return CSE_OK;
+  hipStream_t s = ev->stream;
+  rc = Z.row_begin.upload(Y.row_begin.data(), Y.row_begin.size(), s);
+  if (!rc) rc = Z.col_begin.upload(Y.col_begin.data(), Y.col_begin.size(), s);
+  if (!rc) rc = Z.block_col.upload(Y.block_col.data(), Y.block_col.size(), s);
+  if (!rc) rc = Z.plan_block.upload(Y.plan_block.data(), Y.plan_block.size(), s);
+  if (!rc) rc = Z.sparse_of_plan.upload(Y.sparse_of_plan.data(), Y.sparse_of_plan.size(), s);
+  if (!rc) rc = Z.finish.upload(Y.finish.data(), Y.finish.size(), s);
+  if (!rc) rc = Z.col_block.upload(Y.col_block.data(), Y.col_block.size(), s);
+  if (!rc) rc = Z.contrib.alloc((size_t)(9 * Y.num_blocks));
+  // The copies read Y's tables: wait before Y goes out of scope.
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = Fail(CSE_ERR_HIP, "structure upload failed");
+  if (rc) {
+    for (DevBuf<int32_t>* b : {&Z.block_col, &Z.plan_block, &Z.sparse_of_plan, &Z.finish, &Z.col_block})
+      b->release();
+    Z.row_begin.release();
+    Z.col_begin.release();
+    Z.contrib.release();
+    return rc;
+  }
+  Z.num_finish = (int64_t)Y.finish.size();
+  Z.h_row_begin = std::move(Y.row_begin);
+  Z.h_block_col = std::move(Y.block_col);
+  Z.uploaded = true;
+  return CSE_OK;
+}
+
+cse::SchurPairArgs MakeSchurPairArgs(cse_evaluator* ev) {
+  const auto& S = ev->schur;
   const Group& G = ev->groups[0];
   const auto& Q = S.pairs;
-  hipStream_t s = ev->stream;
-  // Blocks of cameras that share no point stay zero; the rows' padding
-  // [f_cols, ld) is not touched.
-  if (S.f_cols > 0)
-    CSE_HIP(hipMemset2DAsync(d_S, (size_t)ld * sizeof(double), 0, (size_t)S.f_cols * sizeof(double),
-                             (size_t)S.f_cols, s));
-  if (S.D && S.f_cols > 0)
-    hipLaunchKernelGGL(cse::SchurDiagonalFillKernel,
-                       dim3((unsigned)((S.f_cols + cse::kBlockThreads - 1) / cse::kBlockThreads)),
-                       dim3(cse::kBlockThreads), 0, s, S.D, S.e_cols, d_S, ld, S.f_cols);
   cse::SchurPairArgs a{};
   a.ids = G.ids.p;
   a.jac = S.jac;
@@ -1472,6 +1548,103 @@ int cse_schur_complement(cse_evaluator* ev, double* d_S, int64_t ld) {
   a.nblocks = Q.num_blocks;
   a.nchunks = Q.num_chunks;
   a.partial = Q.partial.p;
+  return a;
+}
+}  // namespace
+}  // extern "C++"
+
+int cse_schur_complement_sparse_structure(cse_evaluator* ev, int64_t* num_block_rows, int64_t* num_blocks,
+                                          int64_t* device_bytes, int64_t* row_begin, int32_t* block_col) {
+  int rc = SchurCheck(ev, false);
+  if (rc) return rc;
+  if ((rc = SchurSparsePlanOf(ev, row_begin || block_col))) return rc;
+  const auto& Z = ev->schur.sparse;
+  if (num_block_rows) *num_block_rows = Z.num_block_rows;
+  if (num_blocks) *num_blocks = Z.num_blocks;
+  if (device_bytes) *device_bytes = Z.device_bytes;
+  if (row_begin) std::copy(Z.h_row_begin.begin(), Z.h_row_begin.end(), row_begin);
+  if (block_col) std::copy(Z.h_block_col.begin(), Z.h_block_col.end(), block_col);
+  return CSE_OK;
+}
+
+int cse_schur_complement_sparse(cse_evaluator* ev, double* d_values) {
+  int rc = SchurCheck(ev, true);
+  if (rc) return rc;
+  if (!d_values) return Fail(CSE_ERR_INVALID, "null pointer");
+  if ((rc = SchurSparsePlanOf(ev, true))) return rc;
+  const auto& Q = ev->schur.pairs;
+  const auto& Z = ev->schur.sparse;
+  hipStream_t s = ev->stream;
+  cse::SchurPairArgs a = MakeSchurPairArgs(ev);
+  a.sparse_of_plan = Z.sparse_of_plan.p;
+  a.plan_block = Z.plan_block.p;
+  a.sparse_col = Z.block_col.p;
+  a.finish = Z.finish.p;
+  a.nfinish = Z.num_finish;
+  a.values = d_values;
+  if (Q.num_chunks > 0)
+    hipLaunchKernelGGL((cse::SchurPairChunkKernel<9, true>),
+                       dim3((unsigned)((Q.num_chunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
+                       dim3(cse::kBlockThreads), 0, s, a);
+  if (Z.num_finish > 0) {
+    const int64_t entries = Z.num_finish * cse::kSchurBlockDoubles;
+    hipLaunchKernelGGL((cse::SchurSparseFinishKernel<9>),
+                       dim3((unsigned)((entries + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                       dim3(cse::kBlockThreads), 0, s, a);
+  }
+  CSE_HIP(hipGetLastError());
+  return CSE_OK;
+}
+
+int cse_schur_explicit_multiply(cse_evaluator* ev, const double* d_values, const double* d_x, double* d_y) {
+  int rc = SchurCheck(ev, true);
+  if (rc) return rc;
+  if (!d_values || !d_x || !d_y) return Fail(CSE_ERR_INVALID, "null pointer");
+  // Workgroups assign y while others still read x: the two may not overlap.
+  if (d_x < d_y + ev->schur.f_cols && d_y < d_x + ev->schur.f_cols)
+    return Fail(CSE_ERR_INVALID, "cse_schur_explicit_multiply: x and y overlap");
+  if ((rc = SchurSparsePlanOf(ev, true))) return rc;
+  const auto& Z = ev->schur.sparse;
+  cse::SchurExplicitArgs a{};
+  a.row_begin = Z.row_begin.p;
+  a.col_begin = Z.col_begin.p;
+  a.block_col = Z.block_col.p;
+  a.col_block = Z.col_block.p;
+  a.values = d_values;
+  a.x = d_x;
+  a.y = d_y;
+  a.C = Z.num_block_rows;
+  if (Z.num_block_rows > 0) {
+    // The rows' pass leaves each block's column contribution; the columns'
+    // pass adds them to y in the transposed index's order.
+    hipLaunchKernelGGL((cse::SchurExplicitRowKernel<9>), dim3((unsigned)Z.num_block_rows),
+                       dim3(cse::kSchurExplicitWaves * cse::kWave), 0, ev->stream, a, Z.contrib.p);
+    hipLaunchKernelGGL((cse::SchurExplicitColumnKernel<9>), dim3((unsigned)Z.num_block_rows),
+                       dim3(cse::kBlockThreads), 0, ev->stream, a, (const double*)Z.contrib.p);
+  }
+  CSE_HIP(hipGetLastError());
+  return CSE_OK;
+}
+
+int cse_schur_complement(cse_evaluator* ev, double* d_S, int64_t ld) {
+  int rc = SchurCheck(ev, true);
+  if (rc) return rc;
+  auto& S = ev->schur;
+  if (!d_S) return Fail(CSE_ERR_INVALID, "null pointer");
+  if (ld < S.f_cols) return Fail(CSE_ERR_INVALID, "cse_schur_complement: ld is smaller than num_cols_f");
+  if ((rc = SchurPairPlanOf(ev, true))) return rc;
+  const auto& Q = S.pairs;
+  hipStream_t s = ev->stream;
+  // Blocks of cameras that share no point stay zero; the rows' padding
+  // [f_cols, ld) is not touched.
+  if (S.f_cols > 0)
+    CSE_HIP(hipMemset2DAsync(d_S, (size_t)ld * sizeof(double), 0, (size_t)S.f_cols * sizeof(double),
+                             (size_t)S.f_cols, s));
+  if (S.D && S.f_cols > 0)
+    hipLaunchKernelGGL(cse::SchurDiagonalFillKernel,
+                       dim3((unsigned)((S.f_cols + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                       dim3(cse::kBlockThreads), 0, s, S.D, S.e_cols, d_S, ld, S.f_cols);
+  cse::SchurPairArgs a = MakeSchurPairArgs(ev);
   a.S = d_S;
   a.ld = ld;
   if (Q.num_chunks > 0) {

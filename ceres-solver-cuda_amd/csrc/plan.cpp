@@ -985,4 +985,77 @@ int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPla
   return CSE_OK;
 }
 
+int PlanSchurSparse(const int32_t* ids, int64_t n, const SchurPairPlan& plan, int32_t first_id, int64_t C,
+                    bool counts_only, SchurSparsePlan* sparse) {
+  *sparse = SchurSparsePlan{};
+  if (C < 0) return CseFail(CSE_ERR_INVALID, "block-sparse Schur complement: negative camera count");
+  try {
+    std::vector<bool> seen((size_t)C, false);
+    int64_t observed = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t c = (int64_t)ids[2 * i] - first_id;
+      if (c < 0 || c >= C)
+        return CseFail(CSE_ERR_INVALID, "block-sparse Schur complement: an f block outside the cameras");
+      if (!seen[(size_t)c]) ++observed;
+      seen[(size_t)c] = true;
+    }
+    const int64_t added = C - observed;
+    sparse->num_block_rows = C;
+    sparse->num_blocks = plan.num_blocks + added;
+    if (sparse->num_blocks >= ((int64_t)1 << 31))
+      return CseFail(CSE_ERR_UNSUPPORTED, "block-sparse Schur complement: 2^31 or more blocks");
+    // A block of q chunks has q - 1 beyond its first: at most num_chunks -
+    // num_blocks blocks have several.
+    sparse->finish_capacity = plan.num_chunks - plan.num_blocks + added;
+    sparse->device_bytes = 2 * 8 * (C + 1) + 2 * 4 * sparse->num_blocks + 4 * plan.num_blocks +
+                           4 * sparse->finish_capacity + 4 * (sparse->num_blocks - C) +
+                           8 * 9 * sparse->num_blocks;
+    if (counts_only) return CSE_OK;
+    SchurSparsePlan& S = *sparse;
+    S.row_begin.reserve((size_t)C + 1);
+    S.block_col.reserve((size_t)S.num_blocks);
+    S.plan_block.reserve((size_t)S.num_blocks);
+    S.sparse_of_plan.assign((size_t)plan.num_blocks, -1);
+    S.col_begin.assign((size_t)C + 1, 0);
+    int64_t k = 0;  // the pair plan's blocks come in (row, col) order
+    for (int64_t c = 0; c < C; ++c) {
+      S.row_begin.push_back((int64_t)S.block_col.size());
+      if (!(k < plan.num_blocks && plan.block_row[(size_t)k] - first_id == c &&
+            plan.block_col[(size_t)k] - first_id == c)) {
+        S.finish.push_back((int32_t)S.block_col.size());
+        S.block_col.push_back((int32_t)c);
+        S.plan_block.push_back(-1);
+      }
+      for (; k < plan.num_blocks && plan.block_row[(size_t)k] - first_id == c; ++k) {
+        const int64_t c2 = (int64_t)plan.block_col[(size_t)k] - first_id;
+        const int32_t at = (int32_t)S.block_col.size();
+        if (plan.chunk_off[(size_t)k + 1] - plan.chunk_off[(size_t)k] != 1) S.finish.push_back(at);
+        if (c2 > c) ++S.col_begin[(size_t)c2 + 1];
+        S.sparse_of_plan[(size_t)k] = at;
+        S.block_col.push_back((int32_t)c2);
+        S.plan_block.push_back((int32_t)k);
+      }
+    }
+    S.row_begin.push_back((int64_t)S.block_col.size());
+    if (k != plan.num_blocks || (int64_t)S.block_col.size() != S.num_blocks ||
+        (int64_t)S.finish.size() > S.finish_capacity)
+      return CseFail(CSE_ERR_INVALID, "block-sparse Schur complement: the pair plan is not of these ids");
+    for (int64_t c = 0; c < C; ++c) S.col_begin[(size_t)c + 1] += S.col_begin[(size_t)c];
+    // Blocks in storage order are in ascending row order: so is each column's list.
+    std::vector<int64_t> cursor(S.col_begin.begin(), S.col_begin.end() - 1);
+    S.col_block.resize((size_t)(S.num_blocks - C));
+    S.col_row.resize((size_t)(S.num_blocks - C));
+    for (int64_t c = 0; c < C; ++c)
+      for (int64_t b = S.row_begin[(size_t)c] + 1; b < S.row_begin[(size_t)c + 1]; ++b) {
+        const int64_t j = cursor[(size_t)S.block_col[(size_t)b]]++;
+        S.col_block[(size_t)j] = (int32_t)b;
+        S.col_row[(size_t)j] = (int32_t)c;
+      }
+  } catch (const std::bad_alloc&) {
+    *sparse = SchurSparsePlan{};
+    return CseFail(CSE_ERR_OOM, "block-sparse Schur complement: host allocation failed");
+  }
+  return CSE_OK;
+}
+
 }  // namespace cse

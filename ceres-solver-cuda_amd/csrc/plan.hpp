@@ -291,6 +291,51 @@ struct SchurPairPlan : SchurPairCounts {
 // (pair entries are int32), CSE_ERR_OOM when host memory runs out.
 int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPlan* plan);
 
+// ---- The block-sparse Schur complement (cse_schur_complement_sparse,
+// cse_schur_explicit_multiply): S's upper triangle as block-compressed rows,
+// BlockRandomAccessSparseMatrix's cells (SPARSE_SCHUR, and ITERATIVE_SCHUR's
+// use_explicit_schur_complement).  Cameras are indexed 0 .. C-1 in f-column
+// order; every camera has its diagonal block, observed or not.
+constexpr int kSchurExplicitWaves = 4;  // waves that share one row of the product
+
+// The product's fixed cut of a camera's `len` row blocks over the waves of its
+// workgroup: wave w takes [w per, (w + 1) per) clipped to len.
+constexpr int kSchurExplicitSlots = 28;  // partial sums of a camera's column contributions (28 x 9 threads)
+constexpr int64_t SchurExplicitPer(int64_t len) {
+  return (len + kSchurExplicitWaves - 1) / kSchurExplicitWaves;
+}
+
+struct SchurSparseCounts {
+  int64_t num_block_rows = 0;   // C
+  int64_t num_blocks = 0;       // the pair plan's blocks + the added diagonals
+  int64_t finish_capacity = 0;  // bound on num_finish known from the counts alone
+  int64_t device_bytes = 0;     // device bytes of the tables below (col_row stays on the host)
+                                // and of the product's 72-byte column contribution per block
+};
+struct SchurSparsePlan : SchurSparseCounts {
+  // Block k of row c, k in [row_begin[c], row_begin[c+1]), is S(c, block_col[k]);
+  // block_col ascends inside a row and starts at c.
+  std::vector<int64_t> row_begin;       // [C + 1]
+  std::vector<int32_t> block_col;       // [num_blocks]
+  std::vector<int32_t> plan_block;      // [num_blocks]: the pair plan's block, -1 = added diagonal
+  std::vector<int32_t> sparse_of_plan;  // [pair plan's num_blocks]: the inverse
+  // The blocks the finish kernel writes (several chunks, or an added
+  // diagonal); the others are stored by their one chunk.
+  std::vector<int32_t> finish;          // [num_finish <= finish_capacity]
+  // The transposed index: the blocks of column c above the diagonal are
+  // col_block[j], j in [col_begin[c], col_begin[c+1]), of rows col_row[j],
+  // in ascending row order (the product sums contributions in this order).
+  std::vector<int64_t> col_begin;            // [C + 1]
+  std::vector<int32_t> col_block, col_row;   // [num_blocks - C]
+};
+// From the pair plan of the same ids (a counts-only plan when counts_only):
+// camera index = f block id - first_id, in [0, C).  counts_only fills the
+// SchurSparseCounts part alone (it marks the observed cameras in C bits and
+// builds no table).  CSE_ERR_INVALID when an id falls outside the C cameras,
+// CSE_ERR_UNSUPPORTED at 2^31 or more blocks, CSE_ERR_OOM.
+int PlanSchurSparse(const int32_t* ids, int64_t n, const SchurPairPlan& plan, int32_t first_id, int64_t C,
+                    bool counts_only, SchurSparsePlan* sparse);
+
 }  // namespace cse
 
 #endif  // CSE_PLAN_HPP_

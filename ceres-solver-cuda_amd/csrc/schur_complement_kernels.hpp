@@ -26,6 +26,13 @@
 // No atomics; every sum runs in the plan's order: bit-identical run to run.
 // The caller zeroes S first (blocks of f blocks that share no e block) and
 // writes D^2 on the diagonal (f blocks without residual blocks).
+//
+// The block-sparse output (cse::PlanSchurSparse: the 9 x 9 blocks of S's upper
+// triangle as block-compressed rows, BlockRandomAccessSparseMatrix's cells):
+//   SchurPairChunkKernel<S0, true> + SchurSparseFinishKernel   the same sums
+//       stored block by block (cse_schur_complement_sparse);
+//   SchurExplicitRowKernel + SchurExplicitColumnKernel   y = S x on those
+//       blocks (cse_schur_explicit_multiply).
 #ifndef CSE_SCHUR_COMPLEMENT_KERNELS_HPP_
 #define CSE_SCHUR_COMPLEMENT_KERNELS_HPP_
 
@@ -51,9 +58,21 @@ struct SchurPairArgs {
   double* partial;  // [nchunks][S0 * S0]
   double* S;        // row-major, leading dimension ld
   int64_t ld;
+  // The block-sparse store (kSparse kernels) only: values[k][S0][S0] in the
+  // structure's order (cse::SchurSparsePlan).
+  const int32_t* sparse_of_plan;  // [nblocks]: the sparse block of a plan block
+  const int32_t* plan_block;      // [sparse blocks]: the inverse, -1 = added diagonal
+  const int32_t* sparse_col;      // [sparse blocks]: camera index
+  const int32_t* finish;          // [nfinish]: the sparse blocks the finish writes
+  int64_t nfinish;
+  double* values;
 };
 
-template <int S0>
+// kSparse: the block-sparse store.  The chunk of a block with one chunk adds
+// D^2 and stores the block's S0 x S0 doubles straight into values (a diagonal
+// block from its upper triangle, both ways); the other chunks go to partial
+// as in the dense store.
+template <int S0, bool kSparse = false>
 __global__ __launch_bounds__(kBlockThreads) void SchurPairChunkKernel(const SchurPairArgs a) {
   static_assert(S0 <= 16, "A^T B in one 16 x 16 f64 tile");
   constexpr int kW = 2 * S0;        // doubles per LDS row: F_b row | (Q F_b') row
@@ -120,6 +139,27 @@ __global__ __launch_bounds__(kBlockThreads) void SchurPairChunkKernel(const Schu
     __builtin_amdgcn_wave_barrier();
   }
   // C[m][n]: m = lane / 16 + 4 r, n = lane % 16.
+  if constexpr (kSparse) {
+    if (a.chunk_off[k + 1] - a.chunk_off[k] == 1) {
+      const int32_t c = a.block_row[k];
+      const bool diagonal = c == a.block_col[k];
+      double* out = a.values + (int64_t)a.sparse_of_plan[k] * (S0 * S0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int mm = rsub + 4 * r;
+        if (mm >= S0 || col >= S0 || (diagonal && mm > col)) continue;
+        double v = 0.0;  // the finish's sum of one partial
+        v += acc[r];
+        if (diagonal && mm == col && a.D) {
+          const double d = a.D[a.e_cols + a.f_col_base + (int64_t)S0 * c + mm];
+          v += d * d;
+        }
+        out[mm * S0 + col] = v;
+        if (diagonal) out[col * S0 + mm] = v;
+      }
+      return;
+    }
+  }
   double* out = a.partial + q * (S0 * S0);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -146,6 +186,170 @@ __global__ __launch_bounds__(kBlockThreads) void SchurPairFinishKernel(const Sch
   }
   a.S[row * a.ld + cl] = v;
   a.S[cl * a.ld + row] = v;
+}
+
+// The block-sparse store's finish: one thread per entry of a listed block
+// (several chunks, or a diagonal added for a camera without residual blocks:
+// D^2 or zeros), SchurPairFinishKernel's sums written block by block.
+template <int S0>
+__global__ __launch_bounds__(kBlockThreads) void SchurSparseFinishKernel(const SchurPairArgs a) {
+  const int64_t idx = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x;
+  const int64_t i = idx / (S0 * S0);
+  if (i >= a.nfinish) return;
+  const int e = (int)(idx - i * (S0 * S0));
+  const int m = e / S0, n = e - m * S0;
+  const int64_t kk = a.finish[i];
+  const int64_t k = a.plan_block[kk];
+  double* out = a.values + kk * (S0 * S0);
+  if (k < 0) {
+    double v = 0.0;
+    if (m == n && a.D) {
+      const double d = a.D[a.e_cols + (int64_t)S0 * a.sparse_col[kk] + m];
+      v = d * d;
+    }
+    out[e] = v;
+    return;
+  }
+  const int32_t c = a.block_row[k], c2 = a.block_col[k];
+  if (c == c2 && m > n) return;  // a diagonal block: the upper triangle, mirrored
+  double v = 0.0;
+  for (int64_t q = a.chunk_off[k]; q < a.chunk_off[k + 1]; ++q) v += a.partial[q * (S0 * S0) + e];
+  if (c == c2 && m == n && a.D) {
+    const double d = a.D[a.e_cols + a.f_col_base + (int64_t)S0 * c + m];
+    v += d * d;
+  }
+  out[e] = v;
+  if (c == c2) out[n * S0 + m] = v;
+}
+
+// y = S x from the block-sparse upper triangle, every block read once, in
+// two kernels; no atomics, every sum in a fixed order.
+struct SchurExplicitArgs {
+  const int64_t *row_begin, *col_begin;  // [C + 1]
+  const int32_t* block_col;              // [blocks]
+  const int32_t* col_block;              // [blocks - C]
+  const double* values;                  // [blocks][S0 * S0]
+  const double* x;
+  double* y;
+  int64_t C;
+};
+
+// SchurExplicitRowKernel: camera c's workgroup walks its ROW blocks alone, cut
+// over the waves by SchurExplicitPer(row blocks).  Besides the row sums, each
+// block S(c, c'), c' > c, leaves its column contribution S(c, c')^T x_c, S0
+// doubles, in contrib[block]: per batch of kSchurExplicitBatch blocks the
+// lanes put S[e] x[S0 c + e / S0] into the wave's LDS tile and lane (u, n) adds entries
+// (0..S0, n) of block u in that order.  y = the row sums, per wave in wave
+// order.  SchurExplicitColumnKernel then adds to y of camera c the
+// contributions of its column blocks: slot s of kSchurExplicitSlots sums the
+// list entries s, s + slots, .. in list order, thread i adds the slots in
+// slot order.  Every block of values is read once.  x and y may not overlap
+// (y_c is assigned while other workgroups read x).
+constexpr int kSchurExplicitBatch = 7;  // blocks per batch: S0 lanes each in one wave
+
+template <int S0>
+__global__ __launch_bounds__(kSchurExplicitWaves* kWave) void SchurExplicitRowKernel(
+    const SchurExplicitArgs a, double* contrib) {
+  constexpr int kB = S0 * S0, kU = kSchurExplicitBatch;
+  static_assert(kB > kWave && kB <= 2 * kWave, "two entries a lane");
+  static_assert(kU * S0 <= kWave, "a lane per column sum of a batch");
+  __shared__ double tile_all[kSchurExplicitWaves][kU * kB];
+  __shared__ double sums[kSchurExplicitWaves][kB];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  double* tile = tile_all[wave];
+  const int64_t c = blockIdx.x;
+  const int64_t r0 = a.row_begin[c], nrow = a.row_begin[c + 1] - r0;
+  const int64_t per = SchurExplicitPer(nrow);
+  const int64_t lo = wave * per, hi = lo + per < nrow ? lo + per : nrow;
+  const int e0 = lane, e1 = lane + kWave;
+  const bool two = e1 < kB;
+  const int n0 = e0 % S0, n1 = two ? e1 % S0 : 0, m0 = e0 / S0, m1 = two ? e1 / S0 : 0;
+  const double xm0 = a.x[(int64_t)S0 * c + m0], xm1 = a.x[(int64_t)S0 * c + m1];
+  const int tu = lane / S0, tn = lane - tu * S0;
+  double ra = 0.0, rb = 0.0;
+  for (int64_t base = lo; base < hi; base += kWave) {
+    const int cnt = (int)(hi - base < kWave ? hi - base : kWave);
+    const int my_cam = a.block_col[r0 + base + (lane < cnt ? lane : cnt - 1)];
+    for (int g = 0; g < cnt; g += kU) {
+      double v0[kU], v1[kU], x0[kU], x1[kU];
+      const double* v[kU];
+      const double* xc[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int i = g + u < cnt ? g + u : cnt - 1;  // past the end: the last block again, not used
+        v[u] = a.values + (r0 + base + i) * kB;
+        xc[u] = a.x + (int64_t)S0 * __builtin_amdgcn_readlane(my_cam, i);
+        v0[u] = v[u][e0];
+        x0[u] = xc[u][n0];
+      }
+      if (two) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+          v1[u] = v[u][e1];
+          x1[u] = xc[u][n1];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        if (g + u >= cnt) break;
+        ra += v0[u] * x0[u];
+        tile[u * kB + e0] = v0[u] * xm0;
+        if (two) {
+          rb += v1[u] * x1[u];
+          tile[u * kB + e1] = v1[u] * xm1;
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      // (the diagonal block, first of the row, has no column contribution)
+      if (tu < kU && g + tu < cnt && base + g + tu > 0) {
+        double s = 0.0;
+#pragma unroll
+        for (int m = 0; m < S0; ++m) s += tile[tu * kB + m * S0 + tn];
+        contrib[(r0 + base + g + tu) * S0 + tn] = s;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  sums[wave][e0] = ra;
+  if (two) sums[wave][e1] = rb;
+  __syncthreads();
+  if (threadIdx.x < S0) {
+    const int i = threadIdx.x;
+    double y = 0.0;
+    for (int w = 0; w < kSchurExplicitWaves; ++w) {
+      double r = 0.0;
+      for (int n = 0; n < S0; ++n) r += sums[w][i * S0 + n];
+      y += r;
+    }
+    a.y[(int64_t)S0 * c + i] = y;
+  }
+}
+
+template <int S0>
+__global__ __launch_bounds__(kBlockThreads) void SchurExplicitColumnKernel(const SchurExplicitArgs a,
+                                                                           const double* contrib) {
+  constexpr int kSlots = kSchurExplicitSlots;
+  static_assert(kSlots * S0 <= kBlockThreads, "a thread per slot and entry");
+  __shared__ double part[kSlots][S0];
+  const int64_t c = blockIdx.x;
+  const int64_t t0 = a.col_begin[c], t1 = a.col_begin[c + 1];
+  if (t0 == t1) return;  // the whole workgroup: y keeps its row sums
+  const int s = threadIdx.x / S0, n = threadIdx.x - s * S0;
+  if (s < kSlots) {
+    double acc = 0.0;
+#pragma unroll 4
+    for (int64_t j = t0 + s; j < t1; j += kSlots) acc += contrib[(int64_t)a.col_block[j] * S0 + n];
+    part[s][n] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x < S0) {
+    double r = 0.0;
+    for (int q = 0; q < kSlots; ++q) r += part[q][threadIdx.x];
+    a.y[(int64_t)S0 * c + threadIdx.x] += r;
+  }
 }
 
 // S[k][k] = D_f[k]^2: the diagonal of f blocks without residual blocks (the

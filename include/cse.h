@@ -518,6 +518,42 @@ int cse_schur_complement(cse_evaluator* ev, double* d_S, int64_t ld);
 int cse_schur_complement_plan(cse_evaluator* ev, int64_t* num_blocks,
                               int64_t* num_pairs, int64_t* plan_bytes);
 
+/* The same S as 9x9 blocks of its upper triangle, the cells of the
+ * BlockRandomAccessSparseMatrix that SchurEliminator::Eliminate fills for
+ * SPARSE_SCHUR (schur_complement_solver.cc) and that ITERATIVE_SCHUR multiplies
+ * by under Solver::Options::use_explicit_schur_complement.  Cameras are indexed
+ * 0..C-1, C = num_cols_f / 9, in f-column order.  Same eligibility and
+ * refusals as cse_schur_complement.
+ *
+ * Structure of S's upper triangle as block-compressed rows: for camera c the
+ * blocks [row_begin[c], row_begin[c+1]) with ascending block_col >= c, the
+ * diagonal block first.  EVERY camera has its diagonal block, observed or not
+ * (BlockRandomAccessSparseMatrix always holds the diagonal); off-diagonal
+ * blocks are exactly the co-visible pairs.  Host arrays, any pointer may be
+ * NULL (counts only: nothing is allocated on the device; with row_begin or
+ * block_col the plan and the structure are built and uploaded as the first
+ * cse_schur_complement_sparse would, CSE_ERR_OOM when they do not fit).  Needs
+ * no cse_schur_init.  device_bytes = what cse_schur_complement_sparse and
+ * cse_schur_explicit_multiply will hold on the device besides the values and
+ * cse_schur_complement_plan's plan_bytes. */
+int cse_schur_complement_sparse_structure(cse_evaluator* ev, int64_t* num_block_rows,
+                                          int64_t* num_blocks, int64_t* device_bytes,
+                                          int64_t* row_begin /*[C+1]*/, int32_t* block_col /*[num_blocks]*/);
+
+/* The values: d_values[k][9][9], row-major per block, in structure order;
+ * 81 * num_blocks doubles, every one assigned (a camera without residual
+ * blocks: diag(D^2), or zeros without D).  Each block equals the same block
+ * of cse_schur_complement's dense S bit for bit; diagonal blocks are
+ * symmetric bit for bit.  Needs cse_schur_init (any preconditioner).
+ * Asynchronous on the evaluator's stream, deterministic. */
+int cse_schur_complement_sparse(cse_evaluator* ev, double* d_values);
+
+/* y = S x (assigned, as cse_schur_multiply) from values laid out as above;
+ * x, y: num_cols_f entries that do not overlap (CSE_ERR_INVALID when they
+ * do).  Asynchronous, deterministic, no atomics. */
+int cse_schur_explicit_multiply(cse_evaluator* ev, const double* d_values,
+                                const double* d_x, double* d_y);
+
 /* ---- One host solve, several GPUs --------------------------------------
  * The reference evaluates on one device (ContextImpl's single stream,
  * include/ceres/internal/cuda_buffer.h:98) and Ceres' host solve calls one

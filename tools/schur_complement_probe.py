@@ -24,6 +24,16 @@ cse_schur_multiply alone (nine columns of one camera per product is the most a
 caller could batch).  Algorithmic bytes of the complement are counted from the
 plan (see complement_bytes).
 
+--sparse measures the block-sparse complement instead (same protocol, same
+process, same init): num_blocks and the bytes of its values;
+cse_schur_complement_sparse against the dense cse_schur_complement where the
+dense S fits --max_dense_gb; cse_schur_explicit_multiply against
+cse_schur_multiply, and its rate over its algorithmic bytes (explicit_bytes);
+the driver's "Linear solver" timer with and without
+--use_explicit_schur_complement (after one discarded driver run, the two
+interleaved twice).  A shape whose plan, structure and values
+exceed --max_sparse_gb gets its counts alone.
+
 Writes one JSON document to --out and prints it.
 """
 import argparse
@@ -40,7 +50,9 @@ sys.path.insert(0, os.path.join(REPO, "ceres-solver-cuda_amd"))
 SHAPES = {
     "problem-49-7776": (49, 7776, 31843),
     "problem-1778-993923": (1778, 993923, 5001946),
+    "problem-13682-4456117": (13682, 4456117, 28987644),
 }
+DEFAULT_SHAPES = ["problem-49-7776", "problem-1778-993923"]
 
 
 def complement_bytes(n_pairs, n_chunks, n_blocks, f_cols):
@@ -163,9 +175,121 @@ def probe(name, args):
     return out
 
 
+def explicit_bytes(num_blocks, f_cols):
+    """Bytes the product needs: every block once, x and y once, and the index
+    tables it walks (row_begin and col_begin, block_col, col_block).  The
+    72-byte column contribution each block leaves for the second kernel
+    (written once, read once) is the implementation's, not counted here."""
+    cams = f_cols // 9
+    return 648 * num_blocks + 2 * 8 * f_cols + 2 * 8 * (cams + 1) + 4 * num_blocks + 4 * (num_blocks - cams)
+
+
+def probe_sparse(name, args):
+    import torch
+    import ceres_amd as ca
+    from ceres_amd import _cse, bal, bundle_adjuster
+
+    bal.CONFIGS.setdefault(name, SHAPES[name])
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    f64 = torch.float64
+    prog = bal.synthetic_program(bal.CONFIGS[name], loss=ca.Loss.huber(1.0))
+    ev = ca.Evaluator(prog, device=0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    n, m = prog.num_effective_parameters, prog.num_residuals
+    e_cols, f_cols = ev.schur_structure()
+    t0 = time.perf_counter()
+    plan_blocks, n_pairs, plan_bytes = ev.schur_complement_plan()
+    cams, num_blocks, structure_bytes = ev.schur_complement_sparse_counts()
+    count_s = time.perf_counter() - t0
+    need = structure_bytes + plan_bytes + 648 * num_blocks
+    out = {"shape": name, "observations": int(prog.num_residual_blocks), "f_cols": f_cols, "cameras": cams,
+           "num_blocks": num_blocks, "plan_blocks": plan_blocks, "num_pairs": n_pairs,
+           "upper_triangle_fill": num_blocks / (cams * (cams + 1) / 2),
+           "values_bytes": 648 * num_blocks, "structure_device_bytes": structure_bytes,
+           "plan_bytes": plan_bytes, "device_bytes_needed": need, "dense_S_bytes": 8 * f_cols * f_cols,
+           "counts_host_s": count_s}
+    out["fits"] = need <= args.max_sparse_gb * 2 ** 30
+    if not out["fits"]:
+        ev.close()
+        return out
+    x = torch.from_numpy(prog.state).to(dev)
+    cost = torch.zeros(1, dtype=f64, device=dev)
+    r = torch.empty(m, dtype=f64, device=dev)
+    jac = torch.empty(prog.num_jacobian_values, dtype=f64, device=dev)
+    ev.evaluate_device(x.data_ptr(), cost.data_ptr(), r.data_ptr(), None, jac.data_ptr())
+    assert ev.wait() == 0
+    D = torch.zeros(n, dtype=f64, device=dev)
+    ones = torch.ones(m, dtype=f64, device=dev)
+    ev.left_multiply_device((jac * jac).data_ptr(), ones.data_ptr(), D.data_ptr())
+    D = torch.sqrt(D.clamp_(min=1e-6) / 1e4)
+    b = -r
+    rhs = torch.empty(f_cols, dtype=f64, device=dev)
+    v = torch.randn(f_cols, dtype=f64, device=dev)
+    y = torch.empty(f_cols, dtype=f64, device=dev)
+    ye = torch.empty(f_cols, dtype=f64, device=dev)
+    init = lambda: ev.schur_init_device(jac.data_ptr(), D.data_ptr(), b.data_ptr(), rhs.data_ptr(),
+                                        _cse.SCHUR_JACOBI)
+    init()
+    V = torch.empty(81 * num_blocks, dtype=f64, device=dev)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ev.schur_complement_sparse_device(V.data_ptr())
+    torch.cuda.synchronize()
+    out["first_sparse_complement_with_plan_build_s"] = time.perf_counter() - t0
+    out["multiply"] = event_ms(torch, lambda: ev.schur_multiply_device(v.data_ptr(), y.data_ptr()),
+                               args.warmup, args.reps)
+    out["explicit_multiply"] = event_ms(
+        torch, lambda: ev.schur_explicit_multiply_device(V.data_ptr(), v.data_ptr(), ye.data_ptr()),
+        args.warmup, args.reps)
+    out["sparse_complement"] = event_ms(torch, lambda: ev.schur_complement_sparse_device(V.data_ptr()),
+                                        args.warmup, args.reps)
+    assert ev.wait() == 0
+    out["explicit_vs_multiply_rel"] = float(((ye - y).norm() / y.norm()).item())
+    nbytes = explicit_bytes(num_blocks, f_cols)
+    em = out["explicit_multiply"]["median_ms"]
+    out["explicit_algorithmic_bytes"] = nbytes
+    out["explicit_TB_per_s"] = nbytes / (em * 1e-3) / 1e12
+    out["explicit_over_implicit"] = em / out["multiply"]["median_ms"]
+    if 8 * f_cols * f_cols <= args.max_dense_gb * 2 ** 30:
+        S = torch.empty((f_cols, f_cols), dtype=f64, device=dev)
+        out["dense_complement"] = event_ms(torch, lambda: ev.schur_complement_device(S.data_ptr()),
+                                           args.warmup, args.reps)
+        out["sparse_over_dense_complement"] = (out["sparse_complement"]["median_ms"] /
+                                               out["dense_complement"]["median_ms"])
+        del S
+    # PCG iterations per solve above which forming S pays for itself
+    gain = out["multiply"]["median_ms"] - em
+    out["break_even_iterations"] = out["sparse_complement"]["median_ms"] / gain if gain > 0 else None
+    ev.close()
+    del V, jac
+
+    # The first driver run of a process pays for torch's first use of its
+    # vector kernels inside the "Linear solver" timer: one run is discarded,
+    # and the implicit leg runs on both sides of the explicit one.
+    flag = ["--use_explicit_schur_complement"]
+    legs = (("warmup_discarded", []), ("implicit", []), ("explicit", flag), ("implicit_again", []),
+            ("explicit_again", flag))
+    for label, extra in () if args.skip_driver else legs:
+        argv = ["--synthetic", name, "--robustify", "--point_sigma", "0.05", "--num_iterations",
+                str(args.num_iterations), "--max_schur_gb", str(args.max_sparse_gb)] + extra
+        text = io.StringIO()
+        with contextlib.redirect_stdout(text):
+            c0, c1, rows = bundle_adjuster.main(argv)
+        line = [ln for ln in text.getvalue().splitlines() if ln.strip().startswith("Linear solver")]
+        out["driver_" + label] = {"argv": argv, "initial_cost": c0, "final_cost": c1,
+                                  "ls_iter": [row[6] for row in rows],
+                                  "accepted": [bool(row[7]) for row in rows],
+                                  "linear_solver_timer": line[0].strip() if line else None}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES))
+    ap.add_argument("--shapes", nargs="+", default=DEFAULT_SHAPES, choices=list(SHAPES))
+    ap.add_argument("--sparse", action="store_true", help="the block-sparse complement's legs")
+    ap.add_argument("--max_sparse_gb", type=float, default=200.0)
+    ap.add_argument("--max_dense_gb", type=float, default=16.0)
+    ap.add_argument("--skip_driver", action="store_true", help="--sparse: the kernels' legs alone")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--num_iterations", type=int, default=4)
@@ -176,7 +300,7 @@ def main():
         sys.exit("schur_complement_probe: needs a HIP device")
     doc = {"device": torch.cuda.get_device_name(0), "shapes": []}
     for name in args.shapes:
-        doc["shapes"].append(probe(name, args))
+        doc["shapes"].append(probe_sparse(name, args) if args.sparse else probe(name, args))
         text = json.dumps(doc, indent=1)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
