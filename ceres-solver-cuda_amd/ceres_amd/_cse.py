@@ -61,6 +61,21 @@ SCHUR_IDENTITY = 0
 SCHUR_JACOBI = 1
 SCHUR_SCHUR_JACOBI = 2
 
+# cse_cg_termination (= LinearSolverTerminationType) and cse_cg_reason
+CG_SUCCESS = 0
+CG_NO_CONVERGENCE = 1
+CG_FAILURE = 2
+CG_REASON_MAX_ITERATIONS = 0
+CG_REASON_ZERO_RHS = 1
+CG_REASON_INITIAL_RESIDUAL = 2
+CG_REASON_RHO = 3
+CG_REASON_BETA = 4
+CG_REASON_INDEFINITE = 5
+CG_REASON_ALPHA = 6
+CG_REASON_Q_TOLERANCE = 7
+CG_REASON_R_TOLERANCE = 8
+CG_ZERO_INITIAL_GUESS = 1  # cse_cg_options.flags
+
 # cse_loss_kind
 LOSS_TRIVIAL = 0
 LOSS_HUBER = 1
@@ -132,6 +147,21 @@ class cse_info(C.Structure):
                 ("bytes_residual_eval", C.c_int64)]
 
 
+class cse_cg_options(C.Structure):
+    _fields_ = [("min_num_iterations", C.c_int32), ("max_num_iterations", C.c_int32),
+                ("residual_reset_period", C.c_int32), ("check_period", C.c_int32),
+                ("r_tolerance", C.c_double), ("q_tolerance", C.c_double),
+                ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class cse_cg_summary(C.Structure):
+    _fields_ = [("termination_type", C.c_int32), ("reason", C.c_int32),
+                ("num_iterations", C.c_int32), ("num_iterations_enqueued", C.c_int32),
+                ("num_synchronizations", C.c_int32), ("reserved", C.c_int32),
+                ("norm_rhs", C.c_double), ("norm_r", C.c_double), ("q", C.c_double),
+                ("zeta", C.c_double), ("rho", C.c_double), ("pq", C.c_double)]
+
+
 P_i32 = C.POINTER(C.c_int32)
 P_i64 = C.POINTER(C.c_int64)
 P_f64 = C.POINTER(C.c_double)
@@ -168,6 +198,9 @@ SIGNATURES = {
     "cse_schur_complement_sparse_structure": (C.c_int, [C.c_void_p, P_i64, P_i64, P_i64, P_i64, P_i32]),
     "cse_schur_complement_sparse": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cse_schur_explicit_multiply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cse_cg_default_options": (None, [C.POINTER(cse_cg_options)]),
+    "cse_schur_solve": (C.c_int, [C.c_void_p, C.POINTER(cse_cg_options), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.POINTER(cse_cg_summary)]),
     "cse_create_multi": (C.c_int, [C.POINTER(cse_problem_desc), C.POINTER(cse_options),
                                    P_i32, C.c_int32, C.POINTER(C.c_void_p)]),
     "cse_shard_info": (C.c_int, [C.c_void_p, P_i32, P_i64, P_i32]),
@@ -225,6 +258,18 @@ def lib():
             raise RuntimeError("libcse.so ABI version mismatch")
         _lib = handle
     return _lib
+
+
+def cg_options(**fields):
+    """cse_cg_default_options' values (min 1, max 500, reset period 10, check
+    period 1, r_tolerance -1, q_tolerance 0, no flags) with `fields` set."""
+    o = cse_cg_options()
+    lib().cse_cg_default_options(C.byref(o))
+    for k, v in fields.items():
+        if k not in dict(cse_cg_options._fields_):
+            raise TypeError(f"cse_cg_options has no field {k}")
+        setattr(o, k, v)
+    return o
 
 
 def last_error():

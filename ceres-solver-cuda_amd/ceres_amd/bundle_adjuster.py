@@ -72,10 +72,34 @@ def parse(argv=None):
     ap.add_argument("--preconditioner", default="jacobi",
                     choices=["identity", "jacobi", "schur_jacobi"],
                     help="iterative_schur's preconditioner (bundle_adjuster.cc default: jacobi)")
+    ap.add_argument("--device_pcg", action="store_true",
+                    help="iterative_schur only: the whole PCG as one call (cse_schur_solve: the "
+                         "reference's ConjugateGradientsSolver with its vectors, scalars and stopping "
+                         "tests on the device) instead of the torch loop on the host; with "
+                         "--use_explicit_schur_complement it iterates on the block-sparse S.  Half "
+                         "the host loop's time at 49 cameras, 3 %% behind it at 1,778 (DESIGN 3.6c)")
+    ap.add_argument("--pcg_termination", default="residual", choices=["residual", "quadratic"],
+                    help="residual: |r| <= eta |b| (the host loop's test; r_tolerance = eta, "
+                         "q_tolerance = 0, no residual reset); quadratic: Ceres' LM setting, "
+                         "q_tolerance = eta, r_tolerance = -1 (levenberg_marquardt_strategy.cc:98-103); "
+                         "needs --device_pcg")
+    ap.add_argument("--pcg_check_period", type=int, default=1,
+                    help="--device_pcg: the host looks at the device state after this many enqueued "
+                         "iterations.  Up to period - 1 iterations run past the end (their result is "
+                         "discarded on the device): 4 where the iteration is launch-bound (best "
+                         "measured at 49 cameras; 16 already loses to the trailing iterations), 1 "
+                         "from about a thousand cameras on, where a product is long against a host "
+                         "wait; DESIGN 3.6c")
     args = ap.parse_args(argv)
     if args.use_explicit_schur_complement and args.linear_solver != "iterative_schur":
         raise SystemExit("--use_explicit_schur_complement needs --linear_solver iterative_schur, not "
                          f"{args.linear_solver}")
+    if args.device_pcg and args.linear_solver != "iterative_schur":
+        raise SystemExit(f"--device_pcg needs --linear_solver iterative_schur, not {args.linear_solver}")
+    if args.pcg_termination == "quadratic" and not args.device_pcg:
+        raise SystemExit("--pcg_termination quadratic needs --device_pcg")
+    if args.pcg_check_period < 1:
+        raise SystemExit("--pcg_check_period must be at least 1")
     return args
 
 
@@ -235,6 +259,17 @@ def solve(args):
             ev.schur_explicit_multiply_device(S_values.data_ptr(), d_x, d_y)
     elif args.linear_solver == "iterative_schur":
         schur_op = ev.schur_multiply_device
+    if args.device_pcg:
+        xf_device = torch.empty(f_cols, dtype=f64, device=dev)
+        max_it = args.max_linear_solver_iterations
+        if args.pcg_termination == "quadratic":
+            cg_options = ca._cse.cg_options(q_tolerance=args.eta, r_tolerance=-1.0)
+        else:  # the host loop's test: no residual reset, no quadratic test
+            cg_options = ca._cse.cg_options(r_tolerance=args.eta, q_tolerance=0.0,
+                                            residual_reset_period=max_it + 1)
+        cg_options.max_num_iterations = max_it
+        cg_options.check_period = args.pcg_check_period
+        cg_options.flags = ca._cse.CG_ZERO_INITIAL_GUESS
 
     def schur_solve(lam):
         # IterativeSchurComplementSolver (iterative_schur_complement_solver.cc:
@@ -248,6 +283,16 @@ def solve(args):
             # SolveReducedLinearSystemUsingConjugateGradients
             # (schur_complement_solver.cc): S once, then the PCG on its blocks.
             ev.schur_complement_sparse_device(S_values.data_ptr())
+        if args.device_pcg:
+            # ConjugateGradientsSolver and BackSubstitute in one call; the zero
+            # start as IterativeSchurComplementSolver's.
+            dx = torch.empty(n, dtype=f64, device=dev)
+            summary = ev.schur_solve_device(
+                rhs.data_ptr(), xf_device.data_ptr(), cg_options,
+                S_values.data_ptr() if args.use_explicit_schur_complement else None, dx.data_ptr())
+            if summary.termination_type == ca._cse.CG_FAILURE:
+                raise SystemExit(f"device PCG failed (reason {summary.reason})")
+            return dx, summary.num_iterations
         xf = torch.zeros(f_cols, dtype=f64, device=dev)
         res = rhs.clone()
         z = torch.zeros_like(res)

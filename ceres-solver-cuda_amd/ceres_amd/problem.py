@@ -784,6 +784,19 @@ class Evaluator:
         return _cse.check(_cse.lib().cse_schur_explicit_multiply(self.handle, d_values, d_x, d_y),
                           "cse_schur_explicit_multiply")
 
+    def schur_solve_device(self, d_rhs, d_x, options, d_values=None, d_step=None):
+        """S x = rhs by the reference's preconditioned conjugate gradients, all
+        on the device (cse_schur_solve): options is a _cse.cse_cg_options
+        (_cse.cg_options(...)); d_x holds the initial guess and receives the
+        solution; d_values: schur_complement_sparse_device's values for the
+        explicit operator, None for the implicit one; d_step: None, or
+        num_effective_parameters entries for the back substitution of x.
+        Returns the _cse.cse_cg_summary (termination type, reason, iterations)."""
+        summary = _cse.cse_cg_summary()
+        _cse.check(_cse.lib().cse_schur_solve(self.handle, C.byref(options), d_values, d_rhs, d_x,
+                                              d_step, C.byref(summary)), "cse_schur_solve")
+        return summary
+
     def plus_device(self, d_state, d_delta, d_out):
         """Device-pointer Plus on the evaluator's stream.  Async."""
         return _cse.check(_cse.lib().cse_plus_device(self.handle, d_state, d_delta, d_out),

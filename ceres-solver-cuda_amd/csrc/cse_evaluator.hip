@@ -35,6 +35,7 @@
 #include "plan.hpp"
 #include "schur_kernels.hpp"
 #include "schur_complement_kernels.hpp"
+#include "cg_kernels.h"
 
 namespace cse {
 std::string& LastError();  // layout.cpp: one per thread (cse_last_error reads it here)
@@ -328,6 +329,13 @@ struct cse_evaluator {
       DevBuf<double> contrib;  // [num_blocks][9]: the product's column contributions
     } sparse;
   } schur;
+  // cse_schur_solve's scratch (cg_kernels.hpp): the four vectors p, r, z, tmp
+  // in one buffer and the state, allocated by the first solve.
+  struct Cg {
+    DevBuf<double> vectors;
+    DevBuf<cse::CgState> state;
+    cse::CgState* state_host = nullptr;  // pinned
+  } cg;
 };
 
 namespace {
@@ -1626,6 +1634,147 @@ int cse_schur_explicit_multiply(cse_evaluator* ev, const double* d_values, const
   return CSE_OK;
 }
 
+// ---------------------------------------------------------------------------
+// cse_schur_solve: the reference's conjugate gradients on the device
+// (cg_state.hpp, cg_kernels.hpp)
+// ---------------------------------------------------------------------------
+void cse_cg_default_options(cse_cg_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->min_num_iterations = 1;
+  o->max_num_iterations = 500;
+  o->residual_reset_period = 10;
+  o->check_period = 1;
+  o->r_tolerance = -1.0;
+  o->q_tolerance = 0.0;
+}
+
+extern "C++" {
+namespace {
+
+// The loop of conjugate_gradients_solver.h:108-305 over any operator: `op(x, y)`
+// enqueues y = A x on the stream `s` and returns a cse status; the
+// preconditioner is the one described in `a` (applied inside
+// CgDirectionKernel).  The host enqueues check_period iterations, copies the
+// state to pinned memory, waits once and stops or goes on; it computes no
+// scalar of the iteration.  Nothing is allocated here.
+template <class Op>
+int CgSolve(const cse::CgArgs& a, const cse_cg_options& o, cse::CgState* state_host, hipStream_t s,
+            Op&& op, cse_cg_summary* summary) {
+  int rc;
+  int32_t syncs = 0, enqueued = 0;
+  auto look = [&]() -> int {
+    CSE_HIP(hipMemcpyAsync(state_host, a.state, sizeof(cse::CgState), hipMemcpyDeviceToHost, s));
+    CSE_HIP(hipStreamSynchronize(s));
+    ++syncs;
+    return CSE_OK;
+  };
+  const bool zero_guess = (o.flags & CSE_CG_ZERO_INITIAL_GUESS) != 0;
+  cse::LaunchCgInit(a, zero_guess, s);
+  if (!zero_guess) {
+    if ((rc = op((const double*)a.x, a.tmp))) return rc;
+    cse::LaunchCgInitialResidual(a, s);
+  }
+  CSE_HIP(hipGetLastError());
+  // |b| = 0 and convergence before the first iteration end here.
+  if ((rc = look())) return rc;
+  for (int32_t it = 1; !state_host->done && it <= o.max_num_iterations; ++it) {
+    cse::LaunchCgDirection(a, s);
+    if ((rc = op((const double*)a.p, a.z))) return rc;
+    if (it % o.residual_reset_period == 0) {
+      cse::LaunchCgUpdate(cse::kCgUpdateX, a, s);
+      if ((rc = op((const double*)a.x, a.tmp))) return rc;
+      cse::LaunchCgUpdate(cse::kCgUpdateReset, a, s);
+    } else {
+      cse::LaunchCgUpdate(cse::kCgUpdateFull, a, s);
+    }
+    CSE_HIP(hipGetLastError());
+    ++enqueued;
+    if (enqueued % o.check_period == 0 || it == o.max_num_iterations)
+      if ((rc = look())) return rc;
+  }
+  const cse::CgState& st = *state_host;
+  if (!st.done) return Fail(CSE_ERR_HIP, "cse_schur_solve: the device state did not terminate");
+  summary->termination_type = st.termination_type;
+  summary->reason = st.reason;
+  summary->num_iterations = st.iteration;
+  summary->num_iterations_enqueued = enqueued;
+  summary->num_synchronizations = syncs;
+  summary->reserved = 0;
+  summary->norm_rhs = st.norm_rhs;
+  summary->norm_r = st.norm_r;
+  summary->q = st.Q1;
+  summary->zeta = st.zeta;
+  summary->rho = st.rho;
+  summary->pq = st.pq;
+  return CSE_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const double* d_S_values,
+                    const double* d_rhs, double* d_x, double* d_step, cse_cg_summary* summary) {
+  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
+  CSE_SINGLE_DEVICE(ev, "cse_schur_solve");
+  if (!options || !summary || !d_rhs || !d_x)
+    return Fail(CSE_ERR_INVALID, "cse_schur_solve: null options, summary, d_rhs or d_x");
+  const cse_cg_options& o = *options;
+  if (o.check_period < 1) return Fail(CSE_ERR_INVALID, "cse_schur_solve: check_period is below 1");
+  if (o.residual_reset_period < 1)
+    return Fail(CSE_ERR_INVALID, "cse_schur_solve: residual_reset_period is below 1");
+  if (o.max_num_iterations < 1)
+    return Fail(CSE_ERR_INVALID, "cse_schur_solve: max_num_iterations is below 1");
+  if (o.min_num_iterations < 0)
+    return Fail(CSE_ERR_INVALID, "cse_schur_solve: min_num_iterations is negative");
+  if (o.reserved != 0) return Fail(CSE_ERR_INVALID, "cse_schur_solve: options.reserved is not 0");
+  if (o.flags & ~CSE_CG_ZERO_INITIAL_GUESS) return Fail(CSE_ERR_INVALID, "cse_schur_solve: unknown flags");
+  int rc = SchurCheck(ev, true);
+  if (rc) return rc;
+  auto& S = ev->schur;
+  const int64_t n = S.f_cols;
+  if (d_rhs < d_x + n && d_x < d_rhs + n) return Fail(CSE_ERR_INVALID, "cse_schur_solve: d_x overlaps d_rhs");
+  if (d_S_values && !S.sparse.uploaded)
+    return Fail(CSE_ERR_INVALID,
+                "cse_schur_solve: d_S_values without the block-sparse structure "
+                "(cse_schur_complement_sparse_structure, cse_schur_complement_sparse)");
+  auto& W = ev->cg;
+  if ((rc = W.vectors.ensure((size_t)4 * (size_t)std::max<int64_t>(n, 1)))) return rc;
+  if ((rc = W.state.ensure(1))) return rc;
+  if (!W.state_host) CSE_HIP(hipHostMalloc((void**)&W.state_host, sizeof(cse::CgState)));
+  cse::CgArgs a{};
+  a.n = n;
+  a.rhs = d_rhs;
+  a.x = d_x;
+  a.p = W.vectors.p;
+  a.r = a.p + n;
+  a.z = a.r + n;
+  a.tmp = a.z + n;
+  if (S.preconditioner != CSE_SCHUR_IDENTITY) {
+    // The cameras' inverse blocks start at f index f_col_base + 9 lo
+    // (cse_schur_precondition).
+    const Group::GradPlan& P = ev->groups[0].grad[0];
+    a.precond = S.precond.p;
+    a.pre_off = S.f_col_base + 9LL * P.lo;
+    a.pre_n = 9LL * P.count;
+    if (a.pre_off < 0 || a.pre_off + a.pre_n > n || (size_t)(9 * a.pre_n) > S.precond.n)
+      return Fail(CSE_ERR_INVALID, "cse_schur_solve: the preconditioner's blocks do not fit the f columns");
+  }
+  a.state = W.state.p;
+  a.params = cse::CgParams{o.min_num_iterations, o.max_num_iterations, o.r_tolerance, o.q_tolerance};
+  std::memset(summary, 0, sizeof(*summary));
+  if (d_S_values)
+    rc = CgSolve(a, o, W.state_host, ev->stream,
+                 [&](const double* x, double* y) { return cse_schur_explicit_multiply(ev, d_S_values, x, y); },
+                 summary);
+  else
+    rc = CgSolve(a, o, W.state_host, ev->stream,
+                 [&](const double* x, double* y) { return cse_schur_multiply(ev, x, y); }, summary);
+  if (rc) return rc;
+  if (d_step && summary->termination_type != CSE_CG_FAILURE) return cse_schur_back_substitute(ev, d_x, d_step);
+  return CSE_OK;
+}
+
 int cse_schur_complement(cse_evaluator* ev, double* d_S, int64_t ld) {
   int rc = SchurCheck(ev, true);
   if (rc) return rc;
@@ -1732,6 +1881,7 @@ void cse_destroy(cse_evaluator* ev) {
   (void)hipSetDevice(ev->device);
   if (ev->stream) (void)hipStreamSynchronize(ev->stream);
   if (ev->status_host) (void)hipHostFree(ev->status_host);
+  if (ev->cg.state_host) (void)hipHostFree(ev->cg.state_host);
   for (auto& pr : ev->pending) ev->pool.push_back(pr);
   for (auto& pr : ev->pool) {
     (void)hipEventDestroy(pr.first);
@@ -1910,4 +2060,5 @@ int cse_reset_kernel_stats(cse_evaluator* ev) {
 // line, tests/cpp/Makefile, lists the objects of ABI 5).
 #ifdef CSE_PER_BLOCK_LOSS_IN_THIS_TU
 #include "per_block_loss_kernels.hip"
+#include "cg_kernels.hip"  // with this unit's flags there: no sanitizer run reaches an infinite scalar
 #endif

@@ -554,6 +554,85 @@ int cse_schur_complement_sparse(cse_evaluator* ev, double* d_values);
 int cse_schur_explicit_multiply(cse_evaluator* ev, const double* d_values,
                                 const double* d_x, double* d_y);
 
+/* The solver over these operators: ConjugateGradientsSolver
+ * (internal/ceres/conjugate_gradients_solver.h:108-305) statement for
+ * statement, as IterativeSchurComplementSolver runs it
+ * (iterative_schur_complement_solver.cc:63-170), with every vector, scalar and
+ * stopping test on the device.  The host enqueues check_period iterations,
+ * copies the 96-byte state back, waits once and stops or goes on; iterations
+ * enqueued past the end change nothing, so the result does not depend on
+ * check_period. */
+enum cse_cg_termination {       /* = LinearSolverTerminationType */
+  CSE_CG_SUCCESS = 0,
+  CSE_CG_NO_CONVERGENCE = 1,
+  CSE_CG_FAILURE = 2
+};
+
+enum cse_cg_reason {            /* the statement of the reference that ended it */
+  CSE_CG_REASON_MAX_ITERATIONS = 0,    /* :299-301 */
+  CSE_CG_REASON_ZERO_RHS = 1,          /* :131-136, |b| = 0: x = 0 */
+  CSE_CG_REASON_INITIAL_RESIDUAL = 2,  /* :147-152, min_num_iterations == 0 */
+  CSE_CG_REASON_RHO = 3,               /* :168-172, FAILURE */
+  CSE_CG_REASON_BETA = 4,              /* :178-187, FAILURE */
+  CSE_CG_REASON_INDEFINITE = 5,        /* :196-205, p'q <= 0: NO_CONVERGENCE */
+  CSE_CG_REASON_ALPHA = 6,             /* :208-216, FAILURE */
+  CSE_CG_REASON_Q_TOLERANCE = 7,       /* :273-283 */
+  CSE_CG_REASON_R_TOLERANCE = 8        /* :288-297 */
+};
+
+#define CSE_CG_ZERO_INITIAL_GUESS 1u /* x = 0, r = rhs: no initial product; d_x's
+                                        contents on entry are not read */
+
+typedef struct cse_cg_options {
+  int32_t min_num_iterations;     /* 1   (linear_solver.h:165) */
+  int32_t max_num_iterations;     /* caller sets; cse_cg_default_options: 500 */
+  int32_t residual_reset_period;  /* 10  (linear_solver.h:211) */
+  int32_t check_period;           /* 1: the host looks at the device state after
+                                     every check_period iterations */
+  double  r_tolerance;            /* |r| <= r_tolerance |b|;  <0 disables */
+  double  q_tolerance;            /* i (Q_i - Q_{i-1}) / Q_i < q_tolerance */
+  uint32_t flags;                 /* CSE_CG_ZERO_INITIAL_GUESS */
+  int32_t reserved;               /* 0, checked */
+} cse_cg_options;
+
+typedef struct cse_cg_summary {
+  int32_t termination_type;       /* cse_cg_termination */
+  int32_t reason;                 /* cse_cg_reason */
+  int32_t num_iterations;         /* the reference's summary.num_iterations */
+  int32_t num_iterations_enqueued;
+  int32_t num_synchronizations;   /* host waits on the stream in this call */
+  int32_t reserved;
+  double norm_rhs, norm_r, q, zeta, rho, pq;   /* as last computed (q: Q_i) */
+} cse_cg_summary;
+
+/* min 1, max 500, reset period 10, check period 1, r_tolerance -1,
+ * q_tolerance 0, no flags. */
+void cse_cg_default_options(cse_cg_options* options);
+
+/* Solves S x = rhs by preconditioned conjugate gradients.  Needs
+ * cse_schur_init, whose preconditioner it applies (IDENTITY: z = r).
+ *   d_S_values  NULL: the implicit operator (cse_schur_multiply); else the
+ *               values cse_schur_complement_sparse wrote
+ *               (cse_schur_explicit_multiply); the structure must be uploaded
+ *   d_rhs       num_cols_f, cse_schur_init's d_rhs
+ *   d_x         num_cols_f; in: the initial guess (not read under
+ *               CSE_CG_ZERO_INITIAL_GUESS), out: the solution; may not overlap d_rhs
+ *   d_step      NULL, or num_effective_parameters: cse_schur_back_substitute(x)
+ *               when the termination type is not FAILURE, left alone when it
+ *               is; queued on the stream after the last wait, as that call
+ * Returns CSE_OK for every termination type (the summary says which) after
+ * waiting for the last state on the evaluator's stream; negative for usage
+ * and HIP errors.  CSE_ERR_INVALID: a NULL options, summary, d_rhs or d_x;
+ * check_period, residual_reset_period or max_num_iterations < 1;
+ * min_num_iterations < 0; reserved != 0; unknown flags; d_x overlapping d_rhs;
+ * d_S_values before the sparse structure is uploaded; no cse_schur_init.
+ * CSE_ERR_UNSUPPORTED on a cse_create_multi handle.  Four num_cols_f vectors
+ * and the state are allocated by the first call and kept; deterministic: two
+ * calls with the same inputs give the same bits. */
+int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options,
+                    const double* d_S_values, const double* d_rhs, double* d_x,
+                    double* d_step, cse_cg_summary* summary);
+
 /* ---- One host solve, several GPUs --------------------------------------
  * The reference evaluates on one device (ContextImpl's single stream,
  * include/ceres/internal/cuda_buffer.h:98) and Ceres' host solve calls one
