@@ -1,4 +1,7 @@
-// cse_evaluator.hip -- the C ABI (include/cse.h) over the gfx950 kernels.
+// cse_evaluator.hip -- the C ABI (include/cse.h) over the gfx950 kernels:
+// the user-kind registry, create and upload, the evaluation and Plus.  The
+// calls a linear solver makes on the same evaluator (evaluator.hpp) are in
+// linear_operators.hip.
 //
 // Host side of the evaluator: uploads the Program once
 // (RegisteredCUDAEvaluators::Init, internal/ceres/registered_cuda_evaluators.cc:226-280)
@@ -26,6 +29,8 @@
 #include <vector>
 
 #include "../../include/cse.h"
+#include "evaluation_kernels.hpp"
+#include "evaluator.hpp"
 #include "group_store_kernel.hpp"
 #include "jet_kernels.h"
 #include "kernel_pickers.hpp"
@@ -33,9 +38,6 @@
 #include "multi_device.h"
 #include "per_block_loss_kernels.h"
 #include "plan.hpp"
-#include "schur_kernels.hpp"
-#include "schur_complement_kernels.hpp"
-#include "cg_kernels.h"
 
 namespace cse {
 std::string& LastError();  // layout.cpp: one per thread (cse_last_error reads it here)
@@ -43,6 +45,9 @@ std::string& LastError();  // layout.cpp: one per thread (cse_last_error reads i
 
 namespace {
 
+using cse::DevBuf;
+using cse::Fail;
+using cse::Group;
 using cse::kAffineCrs;
 using cse::kAffinePacked;
 using cse::kKindQuaternionTangent;
@@ -65,25 +70,6 @@ LaunchFn Pick(int kind, int loss, bool jac, int policy, bool dma, bool const0 = 
 LaunchFn PickFused(int kind, int loss, int policy, bool points, bool const0 = false) {
   return cse::PickFused<cse::UniformLosses>(kind, loss, policy, points, const0);
 }
-
-int Fail(int code, const std::string& msg) { return CseFail(code, msg); }
-
-// Entry points whose arguments are device pointers of one device.
-#define CSE_SINGLE_DEVICE(ev, what)                                                         \
-  do {                                                                                     \
-    if ((ev) && (ev)->multi)                                                               \
-      return Fail(CSE_ERR_UNSUPPORTED, std::string(what) +                                 \
-                                           ": not available on a multi-device evaluator " \
-                                           "(cse_create_multi): its outputs span devices"); \
-  } while (0)
-
-#define CSE_HIP(call)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (call);                                                        \
-    if (e_ != hipSuccess)                                                          \
-      return Fail(CSE_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 
 // The planner's shape table (plan.hpp, cse::kKindRows) row by row against
 // the functor types the kernels are instantiated with.
@@ -148,197 +134,11 @@ namespace {
 
 bool ShapeOf(int kind, KindShape* k) { return cse::ShapeOf(kind, UserOps(kind), k); }
 
-// Device buffer, move-only, freed on destruction.
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    if (this != &o) {
-      release();
-      p = o.p, n = o.n;
-      o.p = nullptr, o.n = 0;
-    }
-    return *this;
-  }
-  ~DevBuf() { release(); }
-  int alloc(size_t count) {
-    release();
-    if (count == 0) return CSE_OK;
-    if (hipMalloc(&p, count * sizeof(T)) != hipSuccess) {
-      p = nullptr;
-      return Fail(CSE_ERR_OOM, "hipMalloc of " + std::to_string(count * sizeof(T)) + " bytes failed");
-    }
-    n = count;
-    return CSE_OK;
-  }
-  // Allocate on first use / grow; keeps the buffer when large enough.
-  int ensure(size_t count) {
-    if (p && n >= count) return CSE_OK;
-    return alloc(count);
-  }
-  int upload(const T* h, size_t count, hipStream_t s) {
-    int rc = alloc(count);
-    if (rc) return rc;
-    if (count && hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s) != hipSuccess)
-      return Fail(CSE_ERR_HIP, "hipMemcpyAsync H2D failed");
-    return CSE_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
-
-// A residual group on the device: the planner's decisions (cse::GroupPlan,
-// plan.hpp) and the buffers its tables were uploaded to.
-struct Group : cse::GroupPlan {
-  std::string user_name;
-  DevBuf<int32_t> ids;
-  DevBuf<double> data;       // [n][D]: the functor constants alone
-  DevBuf<double> loss_data;  // [n][2] (a, scale) records: per-block loss parameters only
-  DevBuf<int64_t> gindex;  // only when not contiguous
-  DevBuf<double> packed0;  // repacked slot-0 table (repack0)
-  // Gradient post-pass plan per slot (cse::GradPlanInfo, cse::GradTables).
-  struct GradPlan : cse::GradPlanInfo {
-    DevBuf<int32_t> perm;  // empty = identity
-    DevBuf<int64_t> off;
-    DevBuf<int64_t> chunk_begin, chunk_off;
-    DevBuf<int32_t> chunk_pb;
-    DevBuf<int32_t> chunk_order;
-    DevBuf<double> chunk_partial;
-  } grad[2];
-  // const0 (cse::GroupTables): the active bits, repack sources, delta
-  // offsets and per-chunk first cells.
-  DevBuf<uint32_t> act0;
-  DevBuf<int64_t> src0, fbase, delta0;
-  // Held-camera sectors (HeldSectorFixupKernel): each chunk's two side
-  // slots and the previous chunk with F cells (BSM) or row blocks (CRS).
-  DevBuf<double> side;
-  DevBuf<int32_t> prev_seg;
-  // Fused gradient (cse::FusedGrad): the slot-1 boundary entries and slot-0
-  // contributions of eligible groups (allocated on first use).
-  DevBuf<double> gside, gcontrib;
-  // Slot-0-sorted functor data and slot-1 ids (CameraGradientKernel; built
-  // on first use).
-  DevBuf<double> sdata;
-  DevBuf<int32_t> sid1;
-  bool sorted_ready = false;
-  // Table policy: each 64-block chunk's store runs.
-  DevBuf<int64_t> runs;
-};
-
-
-// Waves per workgroup of the CGNR and Schur chunk kernels (one chunk per
-// wave either way); one wave per workgroup, as the Jacobian kernels are
-// launched, measured slower: S x 2.363 -> 2.410 ms, CGNR 2.596 -> 2.614 ms
-// (profiles/round3/w1c).
-constexpr int kOperatorWavesPerWg = cse::kWavesPerBlock;
-
 // Cost reduction: above this many per-wave partials, kPartialBlocks
 // workgroups sum slices and the last of them finalises
 // (ReduceFinalizeKernel); below, one FinalizeKernel.
 constexpr int64_t kPartialsTwoPass = 4096;
 constexpr int kPartialBlocks = 128;
-
-using cse::FusedKind;
-bool SnavelyShaped(const Group& G) { return cse::SnavelyShaped(G.shape); }
-bool UserFused(const Group& G) { return cse::UserFused(G.user, G.shape); }
-
-
-}  // namespace
-
-struct cse_evaluator {
-  // A multi-device evaluator (cse_create_multi) is a shell around CseMulti;
-  // everything below is unused then.
-  CseMulti* multi = nullptr;
-  int device = 0;
-  int num_cus = 256;  // compute units (grid caps of the Plus kernels)
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  cse_options opts{};
-  int64_t num_parameter_blocks = 0, num_parameters = 0, num_effective = 0, num_constant = 0;
-  int64_t num_residual_blocks = 0, num_residuals = 0, num_jacobian_values = 0;
-  int64_t num_plus_jacobian_values = 0;
-  bool has_layout = false;
-  bool jac_covered = true;  // every Jacobian value is written by some block
-  bool res_covered = true;
-  int64_t bytes_jac = 0, bytes_res = 0;
-  std::vector<Group> groups;
-  int64_t total_wg = 0;
-  bool any_general = false;
-  DevBuf<cse::PbDev> pbs;
-  DevBuf<double> cstate, plus_jac;
-  DevBuf<int64_t> res_layout, jac_layout, jac_offsets;
-  DevBuf<double> partials, partials2;
-  // Program::Plus (cse_plus_device): runs of manifold-free state entries.
-  bool plus_supported = true;
-  std::vector<cse::PlusRun> plus_runs_host;
-  DevBuf<cse::PlusRun> plus_runs;
-  // CSE_MANIFOLD_QUATERNION_EUCLIDEAN blocks: Plus one block per thread.
-  std::vector<cse::QuatPlusBlock> plus_quat_host;
-  DevBuf<cse::QuatPlusBlock> plus_quat;
-  DevBuf<double> h_delta, h_plus;
-  DevBuf<int> status;  // [0] running flag, [1] last status, [2] reduce counter
-  // Host-path buffers (allocated on first use).
-  DevBuf<double> h_state, h_cost, h_res, h_jac, h_grad;
-  DevBuf<double> cg_z;  // cse_cgnr_multiply's z = J x when it cannot fuse
-  int* status_host = nullptr;  // pinned
-  // Evaluate at the same point (CSE_EVAL_SAME_POINT): the packed slot-0
-  // tables hold the state of the last evaluation queued without error, and
-  // h_state the last host state uploaded (cleared by a device-pointer call).
-  bool point_current = false;
-  bool host_state_current = false;
-  // Profiling: one (start, stop) event pair per evaluation around its
-  // group kernels, folded lazily so timing never stalls the launch queue.
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, pool;
-  double last_ms = 0.0, total_ms = 0.0;
-  int64_t launches = 0;
-  // The implicit Schur complement (cse_schur_*): structure found at create
-  // time, values and vectors bound by cse_schur_init.
-  struct Schur : cse::SchurPlan {
-    DevBuf<int64_t> chunk_begin, big;
-    DevBuf<double> ete_inv, precond, partial, ub;
-    bool ready = false;
-    int preconditioner = CSE_SCHUR_IDENTITY;
-    const double *jac = nullptr, *D = nullptr, *b = nullptr;
-    // The explicit complement's pair plan (cse::PlanSchurPairs): counted on
-    // the first plan query, built and uploaded on the first
-    // cse_schur_complement; structure only, so it outlives every init.
-    struct Pairs : cse::SchurPairCounts {
-      bool counted = false, uploaded = false;
-      DevBuf<int32_t> block_row, block_col, chunk_block, pairs;
-      DevBuf<int64_t> pair_begin, chunk_off;
-      DevBuf<double> partial;
-    } pairs;
-    // The block-sparse complement's structure (cse::PlanSchurSparse), cached
-    // the same way; row_begin and block_col stay on the host too, for
-    // cse_schur_complement_sparse_structure.
-    struct Sparse : cse::SchurSparseCounts {
-      bool counted = false, uploaded = false;
-      int64_t num_finish = 0;
-      std::vector<int64_t> h_row_begin;
-      std::vector<int32_t> h_block_col;
-      DevBuf<int64_t> row_begin, col_begin;
-      DevBuf<int32_t> block_col, plan_block, sparse_of_plan, finish, col_block;
-      DevBuf<double> contrib;  // [num_blocks][9]: the product's column contributions
-    } sparse;
-  } schur;
-  // cse_schur_solve's scratch (cg_kernels.hpp): the four vectors p, r, z, tmp
-  // in one buffer and the state, allocated by the first solve.
-  struct Cg {
-    DevBuf<double> vectors;
-    DevBuf<cse::CgState> state;
-    cse::CgState* state_host = nullptr;  // pinned
-  } cg;
-};
-
-namespace {
 
 // The post-pass form of a plan (cse::GradForm) and its chunk table.
 int GradFormOf(const cse::GradArgs& ga, const Group::GradPlan& P) {
@@ -349,10 +149,13 @@ cse::GradChunks GradChunksOf(const Group::GradPlan& P) {
   return cse::GradChunks{P.chunk_begin.p, P.chunk_off.p, P.chunk_partial.p, P.nchunks};
 }
 
-// The post-pass kernels of the built-in shapes (the planner's GradSupported
-// names the same ones); a user kind brings its own (cse_functor_ops.gradient).
+}  // namespace
+
+// evaluator.hpp's functions, which linear_operators.hip calls too.
+namespace cse {
+
 bool LaunchGradPass(int nr, int size, const cse::GradArgs& ga, const Group::GradPlan& P,
-                    hipStream_t s, const cse_functor_ops* user = nullptr, int slot = 0) {
+                    hipStream_t s, const cse_functor_ops* user, int slot) {
   const int form = GradFormOf(ga, P);
   const cse::GradChunks ch = GradChunksOf(P);
   if (user) {
@@ -417,6 +220,56 @@ cse::GroupArgs MakeArgs(cse_evaluator* ev, Group& G, const double* state, double
   return a;
 }
 
+cse::GradArgs SlotGradArgs(const Group& G, int j, const double* jac, const double* res, double* grad) {
+  const Group::GradPlan& P = G.grad[j];
+  cse::GradArgs ga{};
+  ga.jac = jac;
+  for (int r = 0; r < G.shape.nr && r < 3; ++r) ga.jrow[r] = G.jac_base[j][r];
+  ga.jstride = G.jac_stride[j];
+  ga.res = res;
+  ga.res_base = G.res_base;
+  ga.perm = P.perm.p;
+  ga.off = P.off.p;
+  ga.count = P.count;
+  ga.lo = P.lo;
+  ga.grad = grad;
+  ga.delta_base = G.delta_base[j];
+  return ga;
+}
+
+int LaunchContribReduce(const Group::GradPlan& P, const double* gcontrib, const cse::GradArgs& ga,
+                        hipStream_t s) {
+  const cse::GradChunks ch = GradChunksOf(P);
+  if (P.nchunks > 0)
+    hipLaunchKernelGGL((cse::GradientContribKernel<9, 10>),
+                       dim3((unsigned)((P.nchunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
+                       dim3(cse::kBlockThreads), 0, s, gcontrib, P.perm.p, ch, P.chunk_order.p);
+  hipLaunchKernelGGL((cse::GradientChunkReduceKernel<9>),
+                     dim3((unsigned)((ga.count + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                     dim3(cse::kBlockThreads), 0, s, ga, ch);
+  CSE_HIP(hipGetLastError());
+  return CSE_OK;
+}
+
+int LaunchFusedGradTail(const Group& G, double* out, hipStream_t s) {
+  const int64_t entries = 2 * ((G.n + cse::kWave - 1) / cse::kWave);
+  hipLaunchKernelGGL((cse::GradientBoundaryKernel<3>),
+                     dim3((unsigned)((entries + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                     dim3(cse::kBlockThreads), 0, s, G.gside.p, entries, out, G.delta_base[1]);
+  const Group::GradPlan& P = G.grad[0];
+  cse::GradArgs ga{};
+  ga.count = P.count;
+  ga.lo = P.lo;
+  ga.grad = out;
+  ga.delta_base = G.delta_base[0];
+  ga.delta_tab = G.const0 ? G.delta0.p + (P.lo - G.slot0_lo) : nullptr;
+  return LaunchContribReduce(P, G.gcontrib.p, ga, s);
+}
+
+}  // namespace cse
+
+namespace {
+
 int FoldTiming(cse_evaluator* ev) {
   for (auto& pr : ev->pending) {
     float ms = 0.f;
@@ -431,36 +284,8 @@ int FoldTiming(cse_evaluator* ev) {
   return CSE_OK;
 }
 
-// After a fused kernel (the evaluator's FusedGrad or CgnrMultiplyKernel):
-// add the slot-1 boundary entries and the slot-0 contributions, per
-// parameter block in a fixed order, into out (delta offsets).
-int LaunchFusedGradTail(const Group& G, double* out, hipStream_t s) {
-  const int64_t entries = 2 * ((G.n + cse::kWave - 1) / cse::kWave);
-  hipLaunchKernelGGL((cse::GradientBoundaryKernel<3>),
-                     dim3((unsigned)((entries + cse::kBlockThreads - 1) / cse::kBlockThreads)),
-                     dim3(cse::kBlockThreads), 0, s, G.gside.p, entries, out, G.delta_base[1]);
-  const Group::GradPlan& P = G.grad[0];
-  cse::GradArgs ga{};
-  ga.count = P.count;
-  ga.lo = P.lo;
-  ga.grad = out;
-  ga.delta_base = G.delta_base[0];
-  ga.delta_tab = G.const0 ? G.delta0.p + (P.lo - G.slot0_lo) : nullptr;
-  const cse::GradChunks ch{P.chunk_begin.p, P.chunk_off.p, P.chunk_partial.p, P.nchunks};
-  if (P.nchunks > 0)
-    hipLaunchKernelGGL((cse::GradientContribKernel<9, 10>),
-                       dim3((unsigned)((P.nchunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
-                       dim3(cse::kBlockThreads), 0, s, G.gcontrib.p, P.perm.p, ch,
-                       P.chunk_order.p);
-  hipLaunchKernelGGL((cse::GradientChunkReduceKernel<9>),
-                     dim3((unsigned)((ga.count + cse::kBlockThreads - 1) / cse::kBlockThreads)),
-                     dim3(cse::kBlockThreads), 0, s, ga, ch);
-  CSE_HIP(hipGetLastError());
-  return CSE_OK;
-}
-
-// gradient_mode 0: the slot-1 boundary entries as above, and the slot-0
-// sums by re-evaluation in camera order (CameraGradientKernel), then
+// gradient_mode 0: the slot-1 boundary entries as LaunchFusedGradTail's, and
+// the slot-0 sums by re-evaluation in camera order (CameraGradientKernel), then
 // GradientChunkReduceKernel.  The sorted inputs are built on first use
 // (CamGradSortedInputs, on the evaluator's stream).
 int CamGradSortedInputs(Group& G, hipStream_t s) {
@@ -770,20 +595,8 @@ int Enqueue(cse_evaluator* ev, const double* d_state, double* d_cost, double* d_
     } else if (grad_pass) {
       const int sizes[2] = {G.shape.s0, G.shape.s1};
       for (int j = 0; j < G.shape.nb; ++j) {
-        const Group::GradPlan& P = G.grad[j];
-        cse::GradArgs ga{};
-        ga.jac = d_jac;
-        for (int r = 0; r < G.shape.nr && r < 3; ++r) ga.jrow[r] = G.jac_base[j][r];
-        ga.jstride = G.jac_stride[j];
-        ga.res = d_res;
-        ga.res_base = G.res_base;
-        ga.perm = P.perm.p;
-        ga.off = P.off.p;
-        ga.count = P.count;
-        ga.lo = P.lo;
-        ga.grad = d_grad;
-        ga.delta_base = G.delta_base[j];
-        if (!LaunchGradPass(G.shape.nr, sizes[j], ga, P, ev->stream, G.user, j))
+        const cse::GradArgs ga = SlotGradArgs(G, j, d_jac, d_res, d_grad);
+        if (!LaunchGradPass(G.shape.nr, sizes[j], ga, G.grad[j], ev->stream, G.user, j))
           return Fail(CSE_ERR_UNSUPPORTED, "no gradient pass for this shape");
         CSE_HIP(hipGetLastError());
       }
@@ -1037,778 +850,6 @@ int cse_set_plus_jacobians(cse_evaluator* ev, const double* plus_jacobians) {
   return CSE_OK;
 }
 
-extern "C++" {
-namespace {
-
-bool DispatchMultiply(int kind, const cse::GroupArgs& a, bool affine, bool left, const double* x,
-                      double* y, hipStream_t s) {
-  const int which = affine && !left ? 0 : left ? 2 : 1;
-  return VisitKind(kind, [&](auto kd) { cse::LaunchMultiplyKernel<decltype(kd)>(a, which, x, y, s); });
-}
-
-int JacobianMultiply(cse_evaluator* ev, const double* J, const double* x, double* y, bool left) {
-  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
-  CSE_SINGLE_DEVICE(ev, "cse_jacobian_multiply");
-  if (!ev->has_layout)
-    return Fail(CSE_ERR_INVALID, "the descriptor had no Jacobian layout");
-  if (!J || !x || !y) return Fail(CSE_ERR_INVALID, "null pointer");
-  CSE_HIP(hipSetDevice(ev->device));
-  for (auto& G : ev->groups) {
-    if (G.n == 0) continue;
-    // Groups with constant slot-0 blocks take the table kernels (their F
-    // cells are not at affine offsets).
-    const bool affine = G.affine && !G.const0;
-    bool plans = affine;
-    for (int j = 0; j < G.shape.nb; ++j) plans = plans && G.grad[j].ready;
-    // MakeArgs wants non-const outputs; the kernels only read a.jacobian.
-    cse::GroupArgs a = MakeArgs(ev, G, nullptr, nullptr, const_cast<double*>(J), nullptr);
-    if (left && plans) {
-      const int sizes[2] = {G.shape.s0, G.shape.s1};
-      for (int j = 0; j < G.shape.nb; ++j) {
-        const Group::GradPlan& P = G.grad[j];
-        cse::GradArgs ga{};
-        ga.jac = J;
-        for (int r = 0; r < G.shape.nr && r < 3; ++r) ga.jrow[r] = G.jac_base[j][r];
-        ga.jstride = G.jac_stride[j];
-        ga.res = x;
-        ga.res_base = G.res_base;
-        ga.perm = P.perm.p;
-        ga.off = P.off.p;
-        ga.count = P.count;
-        ga.lo = P.lo;
-        ga.grad = y;
-        ga.delta_base = G.delta_base[j];
-        if (!LaunchGradPass(G.shape.nr, sizes[j], ga, P, ev->stream, G.user, j))
-          return Fail(CSE_ERR_UNSUPPORTED, "no J^T x pass for this shape");
-      }
-    } else {
-      if (!G.affine && !ev->any_general)
-        return Fail(CSE_ERR_UNSUPPORTED, "table-path tables were not uploaded");
-      if (G.user) {
-        if (!G.user->multiply)
-          return Fail(CSE_ERR_UNSUPPORTED, "user functor kind " + G.user_name + " has no multiply kernel");
-        G.user->multiply(&a, affine && !left ? 0 : left ? 2 : 1, x, y, ev->stream);
-      } else if (!DispatchMultiply(G.kind, a, affine, left, x, y, ev->stream))
-        return Fail(CSE_ERR_UNSUPPORTED, "no multiply kernel for functor kind " +
-                                             std::to_string(G.kind));
-    }
-    CSE_HIP(hipGetLastError());
-  }
-  return CSE_OK;
-}
-
-}  // namespace
-}  // extern "C++"
-
-int cse_jacobian_right_multiply(cse_evaluator* ev, const double* d_jacobian_values,
-                                const double* d_x, double* d_y) {
-  return JacobianMultiply(ev, d_jacobian_values, d_x, d_y, false);
-}
-
-int cse_jacobian_left_multiply(cse_evaluator* ev, const double* d_jacobian_values,
-                               const double* d_x, double* d_y) {
-  return JacobianMultiply(ev, d_jacobian_values, d_x, d_y, true);
-}
-
-int cse_cgnr_multiply(cse_evaluator* ev, const double* d_jacobian_values, const double* d_D,
-                      const double* d_x, double* d_y) {
-  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
-  CSE_SINGLE_DEVICE(ev, "cse_cgnr_multiply");
-  if (!ev->has_layout) return Fail(CSE_ERR_INVALID, "the descriptor had no Jacobian layout");
-  if (!d_jacobian_values || !d_x || !d_y) return Fail(CSE_ERR_INVALID, "null pointer");
-  CSE_HIP(hipSetDevice(ev->device));
-  hipStream_t s = ev->stream;
-  if (d_D && ev->num_effective > 0)
-    hipLaunchKernelGGL(cse::DtDxpyKernel,
-                       dim3((unsigned)((ev->num_effective + cse::kBlockThreads - 1) / cse::kBlockThreads)),
-                       dim3(cse::kBlockThreads), 0, s, d_D, d_x, d_y, ev->num_effective);
-  bool fused = true;
-  for (auto& G : ev->groups) fused = fused && (G.n == 0 || (G.fuse_ok && !G.const0 && SnavelyShaped(G)));
-  if (!fused) {
-    // z = J x, then y += J^T z: the two products of CudaCgnrLinearOperator.
-    int rc;
-    if ((rc = ev->cg_z.ensure((size_t)std::max<int64_t>(ev->num_residuals, 1)))) return rc;
-    CSE_HIP(hipMemsetAsync(ev->cg_z.p, 0, ev->num_residuals * sizeof(double), s));
-    if ((rc = JacobianMultiply(ev, d_jacobian_values, d_x, ev->cg_z.p, false))) return rc;
-    return JacobianMultiply(ev, d_jacobian_values, ev->cg_z.p, d_y, true);
-  }
-  for (auto& G : ev->groups) {
-    if (G.n == 0) continue;
-    const int64_t chunks = (G.n + cse::kWave - 1) / cse::kWave;
-    int rc;
-    if ((rc = G.gside.ensure((size_t)(2 * chunks * 4)))) return rc;
-    if ((rc = G.gcontrib.ensure((size_t)G.n * G.slot0_stride))) return rc;
-    cse::GroupArgs a = MakeArgs(ev, G, nullptr, nullptr, const_cast<double*>(d_jacobian_values),
-                                nullptr);
-    a.gside = G.gside.p;
-    a.gcontrib = G.gcontrib.p;
-    constexpr int W = kOperatorWavesPerWg;
-    const dim3 grid((unsigned)((chunks + W - 1) / W));
-    if (G.policy == kAffineCrs)
-      hipLaunchKernelGGL((cse::CgnrMultiplyKernel<cse::SnavelyKind, true, W>), grid,
-                         dim3(W * cse::kWave), 0, s, a, d_x, d_y);
-    else
-      hipLaunchKernelGGL((cse::CgnrMultiplyKernel<cse::SnavelyKind, false, W>), grid,
-                         dim3(W * cse::kWave), 0, s, a, d_x, d_y);
-    CSE_HIP(hipGetLastError());
-    if ((rc = LaunchFusedGradTail(G, d_y, s))) return rc;
-  }
-  return CSE_OK;
-}
-
-// ---------------------------------------------------------------------------
-// ITERATIVE_SCHUR on the device (schur_kernels.hpp)
-// ---------------------------------------------------------------------------
-extern "C++" {
-namespace {
-
-cse::SchurArgs MakeSchurArgs(cse_evaluator* ev, const double* x, double* y) {
-  const Group& G = ev->groups[0];
-  const auto& S = ev->schur;
-  cse::SchurArgs a{};
-  a.n = G.n;
-  a.ids = G.ids.p;
-  a.jac = S.jac;
-  a.f_base = G.jac_base[0][0];
-  a.e_base = G.jac_base[1][0];
-  a.f_col_base = S.f_col_base;
-  a.e_col_base = G.delta_base[1];
-  a.e_cols = S.e_cols;
-  a.D = S.D;
-  a.b = S.b;
-  a.b_base = G.res_base;
-  a.x = x;
-  a.ete_inv = S.ete_inv.p;
-  a.contrib = G.gcontrib.p;
-  a.y = y;
-  a.chunk_begin = S.chunk_begin.p;
-  a.nchunks = S.nchunks;
-  a.big = S.big.p;
-  a.nbig = S.nbig;
-  a.status = ev->status.p + 1;  // read by cse_wait
-  return a;
-}
-
-template <int kMode, bool kGrad = false>
-void LaunchSchurPass(const cse::SchurArgs& a, hipStream_t s) {
-  constexpr int W = kOperatorWavesPerWg;
-  if (a.nchunks > 0)
-    hipLaunchKernelGGL((cse::SchurChunkKernel<9, kMode, W, kGrad>), dim3((unsigned)((a.nchunks + W - 1) / W)),
-                       dim3(W * cse::kWave), 0, s, a);
-  if (a.nbig > 0)
-    hipLaunchKernelGGL((cse::SchurBigKernel<9, kMode, kGrad>),
-                       dim3((unsigned)((a.nbig + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
-                       dim3(cse::kBlockThreads), 0, s, a);
-}
-
-// y (f vector) += the per-f-block sums of the contributions just written.
-int SchurFTail(cse_evaluator* ev, double* y, hipStream_t s) {
-  const Group& G = ev->groups[0];
-  const Group::GradPlan& P = G.grad[0];
-  cse::GradArgs ga{};
-  ga.count = P.count;
-  ga.lo = P.lo;
-  ga.grad = y;
-  ga.delta_base = ev->schur.f_col_base;
-  const cse::GradChunks ch{P.chunk_begin.p, P.chunk_off.p, P.chunk_partial.p, P.nchunks};
-  if (P.nchunks > 0)
-    hipLaunchKernelGGL((cse::GradientContribKernel<9, 10>),
-                       dim3((unsigned)((P.nchunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
-                       dim3(cse::kBlockThreads), 0, s, G.gcontrib.p, P.perm.p, ch,
-                       P.chunk_order.p);
-  hipLaunchKernelGGL((cse::GradientChunkReduceKernel<9>),
-                     dim3((unsigned)((ga.count + cse::kBlockThreads - 1) / cse::kBlockThreads)),
-                     dim3(cse::kBlockThreads), 0, s, ga, ch);
-  CSE_HIP(hipGetLastError());
-  return CSE_OK;
-}
-
-// The init's camera-order pass and the per-camera finish (schur_kernels.hpp).
-struct SchurCameraLaunch {
-  cse::SchurArgs a;
-  const Group::GradPlan* P;
-  cse::GradChunks ch;
-  const double* D;
-  int64_t d_off;  // D index of the plan's first camera's first column
-  double* precond;
-  int* status;
-  double* rhs;   // rhs row of the plan's first camera
-  double* grad;  // gradient row of the plan's first camera (null: no gradient)
-};
-
-template <int kDiag, bool kGrad>
-void LaunchSchurCameraPass(const SchurCameraLaunch& L, hipStream_t s) {
-  const Group::GradPlan& P = *L.P;
-  if (P.nchunks > 0)
-    hipLaunchKernelGGL((cse::SchurCameraPassKernel<9, kDiag, kGrad>),
-                       dim3((unsigned)((P.nchunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
-                       dim3(cse::kBlockThreads), 0, s, L.a, P.perm.p, L.ch, P.chunk_order.p);
-  if (P.count > 0)
-    hipLaunchKernelGGL((cse::SchurCameraFinishKernel<9, kDiag, kGrad>),
-                       dim3((unsigned)((P.count + 63) / 64)), dim3(64), 0, s, L.ch, P.count, L.D,
-                       L.d_off, L.precond, L.status, L.rhs, L.grad);
-}
-
-int SchurCheck(cse_evaluator* ev, bool need_ready) {
-  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
-  CSE_SINGLE_DEVICE(ev, "cse_schur");
-  if (!ev->schur.eligible)
-    return Fail(CSE_ERR_UNSUPPORTED,
-                "implicit Schur complement: needs one Snavely-shaped group (2 residuals, blocks of 9 and 3) "
-                "on the affine BlockSparse path "
-                "with its points (slot 1) as the leading e columns and its cameras after them");
-  if (need_ready && !ev->schur.ready) return Fail(CSE_ERR_INVALID, "cse_schur_init has not run");
-  CSE_HIP(hipSetDevice(ev->device));
-  return CSE_OK;
-}
-
-}  // namespace
-}  // extern "C++"
-
-int cse_schur_structure(cse_evaluator* ev, int64_t* num_cols_e, int64_t* num_cols_f) {
-  int rc = SchurCheck(ev, false);
-  if (rc) return rc;
-  if (num_cols_e) *num_cols_e = ev->schur.e_cols;
-  if (num_cols_f) *num_cols_f = ev->schur.f_cols;
-  return CSE_OK;
-}
-
-extern "C++" {
-namespace {
-int SchurInit(cse_evaluator* ev, const double* d_jacobian_values, const double* d_D, const double* d_b,
-              double* d_rhs, int preconditioner, double* d_gradient) {
-  int rc = SchurCheck(ev, false);
-  if (rc) return rc;
-  if (!d_jacobian_values || !d_b || !d_rhs) return Fail(CSE_ERR_INVALID, "null pointer");
-  auto& S = ev->schur;
-  if (preconditioner != CSE_SCHUR_IDENTITY && preconditioner != CSE_SCHUR_JACOBI &&
-      preconditioner != CSE_SCHUR_SCHUR_JACOBI)
-    return Fail(CSE_ERR_INVALID, "unknown preconditioner");
-  if (preconditioner == CSE_SCHUR_SCHUR_JACOBI && S.duplicates)
-    return Fail(CSE_ERR_UNSUPPORTED,
-                "SCHUR_JACOBI: an e block sees one f block in two residual blocks");
-  Group& G = ev->groups[0];
-  hipStream_t s = ev->stream;
-  const bool grad = d_gradient != nullptr;
-  if ((rc = S.ete_inv.ensure((size_t)2 * S.e_cols))) return rc;
-  if ((rc = G.gcontrib.ensure((size_t)G.n * G.slot0_stride))) return rc;  // the multiplies'
-  if ((rc = S.ub.ensure((size_t)G.n * (grad ? 4 : 2)))) return rc;
-  S.jac = d_jacobian_values;
-  S.D = d_D;
-  S.b = d_b;
-  S.preconditioner = preconditioner;
-  // Point order: M_p, u_b = b_b - E_b M_p E_b^T b (and the gradient's e
-  // rows); then camera order: rhs = F^T u, the gradient's f rows -F^T b and
-  // the preconditioner's F^T Q F, each F cell read once.  The status word
-  // read by cse_wait reports a non-positive pivot (schur_kernels.hpp, PivotOk).
-  CSE_HIP(hipMemsetAsync(ev->status.p + 1, 0, sizeof(int), s));
-  CSE_HIP(hipMemsetAsync(d_rhs, 0, S.f_cols * sizeof(double), s));
-  if (grad)  // rows of blocks without residual blocks stay 0
-    CSE_HIP(hipMemsetAsync(d_gradient, 0, ev->num_effective * sizeof(double), s));
-  cse::SchurArgs a = MakeSchurArgs(ev, nullptr, nullptr);
-  a.ub = S.ub.p;
-  a.grad = d_gradient;
-  if (grad)
-    LaunchSchurPass<cse::kSchurInit, true>(a, s);
-  else
-    LaunchSchurPass<cse::kSchurInit>(a, s);
-  CSE_HIP(hipGetLastError());
-  const Group::GradPlan& P = G.grad[0];
-  const int diag = preconditioner == CSE_SCHUR_IDENTITY ? 0 : preconditioner == CSE_SCHUR_JACOBI ? 1 : 2;
-  const int parts = (diag ? cse::SymCount<9>() : 0) + 9 * (grad ? 2 : 1);
-  if ((rc = S.partial.ensure((size_t)std::max<int64_t>(1, P.nchunks) * parts))) return rc;
-  if (diag && (rc = S.precond.ensure((size_t)81 * P.count))) return rc;
-  const cse::GradChunks ch{P.chunk_begin.p, P.chunk_off.p, S.partial.p, P.nchunks};
-  // d_off: D index of camera lo + p = e_cols + f index = e_cols + f_col_base + 9 (lo + p).
-  const int64_t d_off = S.e_cols + S.f_col_base + 9LL * P.lo;
-  double* rhs_p = d_rhs + S.f_col_base + 9LL * P.lo;
-  double* grad_p = grad ? d_gradient + G.delta_base[0] + 9LL * P.lo : nullptr;
-  int* status = ev->status.p + 1;
-  const SchurCameraLaunch L{a, &P, ch, d_D, d_off, S.precond.p, status, rhs_p, grad_p};
-  switch (diag * 2 + (grad ? 1 : 0)) {
-    case 0: LaunchSchurCameraPass<0, false>(L, s); break;
-    case 1: LaunchSchurCameraPass<0, true>(L, s); break;
-    case 2: LaunchSchurCameraPass<1, false>(L, s); break;
-    case 3: LaunchSchurCameraPass<1, true>(L, s); break;
-    case 4: LaunchSchurCameraPass<2, false>(L, s); break;
-    default: LaunchSchurCameraPass<2, true>(L, s); break;
-  }
-  CSE_HIP(hipGetLastError());
-  S.ready = true;
-  return CSE_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int cse_schur_init(cse_evaluator* ev, const double* d_jacobian_values, const double* d_D,
-                   const double* d_b, double* d_rhs, int preconditioner) {
-  return SchurInit(ev, d_jacobian_values, d_D, d_b, d_rhs, preconditioner, nullptr);
-}
-
-int cse_schur_init_gradient(cse_evaluator* ev, const double* d_jacobian_values, const double* d_D,
-                            const double* d_b, double* d_rhs, int preconditioner,
-                            double* d_gradient) {
-  if (!d_gradient) return Fail(CSE_ERR_INVALID, "null gradient");
-  return SchurInit(ev, d_jacobian_values, d_D, d_b, d_rhs, preconditioner, d_gradient);
-}
-
-int cse_schur_multiply(cse_evaluator* ev, const double* d_x, double* d_y) {
-  int rc = SchurCheck(ev, true);
-  if (rc) return rc;
-  if (!d_x || !d_y) return Fail(CSE_ERR_INVALID, "null pointer");
-  const auto& S = ev->schur;
-  hipStream_t s = ev->stream;
-  hipLaunchKernelGGL(cse::SchurDiagKernel,
-                     dim3((unsigned)((S.f_cols + cse::kBlockThreads - 1) / cse::kBlockThreads)),
-                     dim3(cse::kBlockThreads), 0, s, S.D, S.e_cols, d_x, d_y, S.f_cols);
-  LaunchSchurPass<cse::kSchurMultiply>(MakeSchurArgs(ev, d_x, nullptr), s);
-  CSE_HIP(hipGetLastError());
-  return SchurFTail(ev, d_y, s);
-}
-
-int cse_schur_precondition(cse_evaluator* ev, const double* d_x, double* d_y) {
-  int rc = SchurCheck(ev, true);
-  if (rc) return rc;
-  if (!d_x || !d_y) return Fail(CSE_ERR_INVALID, "null pointer");
-  const auto& S = ev->schur;
-  hipStream_t s = ev->stream;
-  const unsigned grid = (unsigned)((S.f_cols + cse::kBlockThreads - 1) / cse::kBlockThreads);
-  if (S.preconditioner == CSE_SCHUR_IDENTITY) {  // IdentityPreconditioner: y += x
-    hipLaunchKernelGGL(cse::AxpyKernel, dim3(grid), dim3(cse::kBlockThreads), 0, s, d_x, d_y,
-                       S.f_cols);
-    CSE_HIP(hipGetLastError());
-    return CSE_OK;
-  }
-  const Group::GradPlan& P = ev->groups[0].grad[0];
-  // The cameras' f rows start at f index f_col_base + 9 lo.
-  const int64_t off = S.f_col_base + 9LL * P.lo;
-  hipLaunchKernelGGL((cse::SchurPrecondApplyKernel<9>), dim3(grid), dim3(cse::kBlockThreads), 0, s,
-                     S.precond.p, d_x + off, d_y + off, 9LL * P.count);
-  CSE_HIP(hipGetLastError());
-  return CSE_OK;
-}
-
-int cse_schur_back_substitute(cse_evaluator* ev, const double* d_x, double* d_y) {
-  int rc = SchurCheck(ev, true);
-  if (rc) return rc;
-  if (!d_x || !d_y) return Fail(CSE_ERR_INVALID, "null pointer");
-  const auto& S = ev->schur;
-  hipStream_t s = ev->stream;
-  // e part: (E^T E + D_e^2)^-1 E^T (b - F x); f part: x.
-  CSE_HIP(hipMemsetAsync(d_y, 0, S.e_cols * sizeof(double), s));
-  LaunchSchurPass<cse::kSchurBack>(MakeSchurArgs(ev, d_x, d_y), s);
-  CSE_HIP(hipGetLastError());
-  CSE_HIP(hipMemcpyAsync(d_y + S.e_cols, d_x, S.f_cols * sizeof(double), hipMemcpyDeviceToDevice, s));
-  return CSE_OK;
-}
-
-extern "C++" {
-namespace {
-// The pair plan of the explicit complement, from the group's ids as they were
-// uploaded (the descriptor is gone after cse_create).
-int SchurIds(cse_evaluator* ev, std::vector<int32_t>* ids) {
-  const Group& G = ev->groups[0];
-  ids->resize((size_t)(2 * G.n));
-  CSE_HIP(hipStreamSynchronize(ev->stream));
-  if (G.n > 0) CSE_HIP(hipMemcpy(ids->data(), G.ids.p, ids->size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return CSE_OK;
-}
-
-// keep: receives the host tables of a plan built by this call (the
-// block-sparse structure is made from them); have_ids: the ids, when the
-// caller has downloaded them already.
-int SchurPairPlanOf(cse_evaluator* ev, bool upload, cse::SchurPairPlan* keep = nullptr,
-                    const std::vector<int32_t>* have_ids = nullptr) {
-  auto& Q = ev->schur.pairs;
-  if (upload ? Q.uploaded : Q.counted) return CSE_OK;
-  const Group& G = ev->groups[0];
-  std::vector<int32_t> own;
-  int rc = have_ids ? CSE_OK : SchurIds(ev, &own);
-  if (rc) return rc;
-  const std::vector<int32_t>& ids = have_ids ? *have_ids : own;
-  cse::SchurPairPlan P;
-  rc = cse::PlanSchurPairs(ids.data(), G.n, !upload, &P);
-  if (rc) return rc;
-  static_cast<cse::SchurPairCounts&>(Q) = P;
-  Q.counted = true;
-  if (!upload) return CSE_OK;
-  hipStream_t s = ev->stream;
-  rc = Q.block_row.upload(P.block_row.data(), P.block_row.size(), s);
-  if (!rc) rc = Q.block_col.upload(P.block_col.data(), P.block_col.size(), s);
-  if (!rc) rc = Q.pair_begin.upload(P.pair_begin.data(), P.pair_begin.size(), s);
-  if (!rc) rc = Q.chunk_off.upload(P.chunk_off.data(), P.chunk_off.size(), s);
-  if (!rc) rc = Q.chunk_block.upload(P.chunk_block.data(), P.chunk_block.size(), s);
-  if (!rc) rc = Q.pairs.upload(P.pairs.data(), P.pairs.size(), s);
-  if (!rc) rc = Q.partial.alloc((size_t)(P.num_chunks * cse::kSchurBlockDoubles));
-  // The copies read P's tables: wait before P goes out of scope.
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = Fail(CSE_ERR_HIP, "plan upload failed");
-  if (rc) {
-    for (DevBuf<int32_t>* b : {&Q.block_row, &Q.block_col, &Q.chunk_block, &Q.pairs}) b->release();
-    Q.pair_begin.release();
-    Q.chunk_off.release();
-    Q.partial.release();
-    return rc;
-  }
-  Q.uploaded = true;
-  if (keep) *keep = std::move(P);  // the host tables, for the block-sparse structure
-  return CSE_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int cse_schur_complement_plan(cse_evaluator* ev, int64_t* num_blocks, int64_t* num_pairs,
-                              int64_t* plan_bytes) {
-  int rc = SchurCheck(ev, false);
-  if (rc) return rc;
-  if ((rc = SchurPairPlanOf(ev, false))) return rc;
-  const auto& Q = ev->schur.pairs;
-  if (num_blocks) *num_blocks = Q.num_blocks;
-  if (num_pairs) *num_pairs = Q.num_pairs;
-  if (plan_bytes) *plan_bytes = Q.plan_bytes;
-  return CSE_OK;
-}
-
-extern "C++" {
-namespace {
-// The block-sparse structure over the pair plan (both built and uploaded when
-// upload; counts alone otherwise).
-int SchurSparsePlanOf(cse_evaluator* ev, bool upload) {
-  auto& Z = ev->schur.sparse;
-  if (upload ? Z.uploaded : Z.counted) return CSE_OK;
-  const Group& G = ev->groups[0];
-  std::vector<int32_t> ids;
-  int rc = SchurIds(ev, &ids);
-  if (rc) return rc;
-  cse::SchurPairPlan P;
-  if ((rc = SchurPairPlanOf(ev, upload, &P, &ids))) return rc;
-  // f index of f block id = f_col_base + 9 id, and camera 0 is f index 0.
-  const int32_t first_id = (int32_t)(-ev->schur.f_col_base / 9);
-  const int64_t C = ev->schur.f_cols / 9;
-  if (upload && P.pair_begin.empty()) {
-    // An earlier call uploaded the pair plan: the block-level tables that the
-    // structure is made from come back from the device.
-    const auto& Q = ev->schur.pairs;
-    try {
-      P.block_row.resize((size_t)Q.num_blocks);
-      P.block_col.resize((size_t)Q.num_blocks);
-      P.chunk_off.resize((size_t)Q.num_blocks + 1);
-    } catch (const std::bad_alloc&) {
-      return Fail(CSE_ERR_OOM, "block-sparse Schur complement: host allocation failed");
-    }
-    if (Q.num_blocks > 0) {
-      CSE_HIP(hipMemcpy(P.block_row.data(), Q.block_row.p, P.block_row.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-      CSE_HIP(hipMemcpy(P.block_col.data(), Q.block_col.p, P.block_col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    CSE_HIP(hipMemcpy(P.chunk_off.data(), Q.chunk_off.p, P.chunk_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-  }
-  static_cast<cse::SchurPairCounts&>(P) = ev->schur.pairs;
-  cse::SchurSparsePlan Y;
-  if ((rc = cse::PlanSchurSparse(ids.data(), G.n, P, first_id, C, !upload, &Y))) return rc;
-  static_cast<cse::SchurSparseCounts&>(Z) = Y;
-  Z.counted = true;
-  if (!upload) return CSE_OK;
-  hipStream_t s = ev->stream;
-  rc = Z.row_begin.upload(Y.row_begin.data(), Y.row_begin.size(), s);
-  if (!rc) rc = Z.col_begin.upload(Y.col_begin.data(), Y.col_begin.size(), s);
-  if (!rc) rc = Z.block_col.upload(Y.block_col.data(), Y.block_col.size(), s);
-  if (!rc) rc = Z.plan_block.upload(Y.plan_block.data(), Y.plan_block.size(), s);
-  if (!rc) rc = Z.sparse_of_plan.upload(Y.sparse_of_plan.data(), Y.sparse_of_plan.size(), s);
-  if (!rc) rc = Z.finish.upload(Y.finish.data(), Y.finish.size(), s);
-  if (!rc) rc = Z.col_block.upload(Y.col_block.data(), Y.col_block.size(), s);
-  if (!rc) rc = Z.contrib.alloc((size_t)(9 * Y.num_blocks));
-  // The copies read Y's tables: wait before Y goes out of scope.
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = Fail(CSE_ERR_HIP, "structure upload failed");
-  if (rc) {
-    for (DevBuf<int32_t>* b : {&Z.block_col, &Z.plan_block, &Z.sparse_of_plan, &Z.finish, &Z.col_block})
-      b->release();
-    Z.row_begin.release();
-    Z.col_begin.release();
-    Z.contrib.release();
-    return rc;
-  }
-  Z.num_finish = (int64_t)Y.finish.size();
-  Z.h_row_begin = std::move(Y.row_begin);
-  Z.h_block_col = std::move(Y.block_col);
-  Z.uploaded = true;
-  return CSE_OK;
-}
-
-cse::SchurPairArgs MakeSchurPairArgs(cse_evaluator* ev) {
-  const auto& S = ev->schur;
-  const Group& G = ev->groups[0];
-  const auto& Q = S.pairs;
-  cse::SchurPairArgs a{};
-  a.ids = G.ids.p;
-  a.jac = S.jac;
-  a.f_base = G.jac_base[0][0];
-  a.e_base = G.jac_base[1][0];
-  a.f_col_base = S.f_col_base;
-  a.e_col_base = G.delta_base[1];
-  a.e_cols = S.e_cols;
-  a.D = S.D;
-  a.ete_inv = S.ete_inv.p;
-  a.block_row = Q.block_row.p;
-  a.block_col = Q.block_col.p;
-  a.pair_begin = Q.pair_begin.p;
-  a.chunk_off = Q.chunk_off.p;
-  a.chunk_block = Q.chunk_block.p;
-  a.pairs = Q.pairs.p;
-  a.nblocks = Q.num_blocks;
-  a.nchunks = Q.num_chunks;
-  a.partial = Q.partial.p;
-  return a;
-}
-}  // namespace
-}  // extern "C++"
-
-int cse_schur_complement_sparse_structure(cse_evaluator* ev, int64_t* num_block_rows, int64_t* num_blocks,
-                                          int64_t* device_bytes, int64_t* row_begin, int32_t* block_col) {
-  int rc = SchurCheck(ev, false);
-  if (rc) return rc;
-  if ((rc = SchurSparsePlanOf(ev, row_begin || block_col))) return rc;
-  const auto& Z = ev->schur.sparse;
-  if (num_block_rows) *num_block_rows = Z.num_block_rows;
-  if (num_blocks) *num_blocks = Z.num_blocks;
-  if (device_bytes) *device_bytes = Z.device_bytes;
-  if (row_begin) std::copy(Z.h_row_begin.begin(), Z.h_row_begin.end(), row_begin);
-  if (block_col) std::copy(Z.h_block_col.begin(), Z.h_block_col.end(), block_col);
-  return CSE_OK;
-}
-
-int cse_schur_complement_sparse(cse_evaluator* ev, double* d_values) {
-  int rc = SchurCheck(ev, true);
-  if (rc) return rc;
-  if (!d_values) return Fail(CSE_ERR_INVALID, "null pointer");
-  if ((rc = SchurSparsePlanOf(ev, true))) return rc;
-  const auto& Q = ev->schur.pairs;
-  const auto& Z = ev->schur.sparse;
-  hipStream_t s = ev->stream;
-  cse::SchurPairArgs a = MakeSchurPairArgs(ev);
-  a.sparse_of_plan = Z.sparse_of_plan.p;
-  a.plan_block = Z.plan_block.p;
-  a.sparse_col = Z.block_col.p;
-  a.finish = Z.finish.p;
-  a.nfinish = Z.num_finish;
-  a.values = d_values;
-  if (Q.num_chunks > 0)
-    hipLaunchKernelGGL((cse::SchurPairChunkKernel<9, true>),
-                       dim3((unsigned)((Q.num_chunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
-                       dim3(cse::kBlockThreads), 0, s, a);
-  if (Z.num_finish > 0) {
-    const int64_t entries = Z.num_finish * cse::kSchurBlockDoubles;
-    hipLaunchKernelGGL((cse::SchurSparseFinishKernel<9>),
-                       dim3((unsigned)((entries + cse::kBlockThreads - 1) / cse::kBlockThreads)),
-                       dim3(cse::kBlockThreads), 0, s, a);
-  }
-  CSE_HIP(hipGetLastError());
-  return CSE_OK;
-}
-
-int cse_schur_explicit_multiply(cse_evaluator* ev, const double* d_values, const double* d_x, double* d_y) {
-  int rc = SchurCheck(ev, true);
-  if (rc) return rc;
-  if (!d_values || !d_x || !d_y) return Fail(CSE_ERR_INVALID, "null pointer");
-  // Workgroups assign y while others still read x: the two may not overlap.
-  if (d_x < d_y + ev->schur.f_cols && d_y < d_x + ev->schur.f_cols)
-    return Fail(CSE_ERR_INVALID, "cse_schur_explicit_multiply: x and y overlap");
-  if ((rc = SchurSparsePlanOf(ev, true))) return rc;
-  const auto& Z = ev->schur.sparse;
-  cse::SchurExplicitArgs a{};
-  a.row_begin = Z.row_begin.p;
-  a.col_begin = Z.col_begin.p;
-  a.block_col = Z.block_col.p;
-  a.col_block = Z.col_block.p;
-  a.values = d_values;
-  a.x = d_x;
-  a.y = d_y;
-  a.C = Z.num_block_rows;
-  if (Z.num_block_rows > 0) {
-    // The rows' pass leaves each block's column contribution; the columns'
-    // pass adds them to y in the transposed index's order.
-    hipLaunchKernelGGL((cse::SchurExplicitRowKernel<9>), dim3((unsigned)Z.num_block_rows),
-                       dim3(cse::kSchurExplicitWaves * cse::kWave), 0, ev->stream, a, Z.contrib.p);
-    hipLaunchKernelGGL((cse::SchurExplicitColumnKernel<9>), dim3((unsigned)Z.num_block_rows),
-                       dim3(cse::kBlockThreads), 0, ev->stream, a, (const double*)Z.contrib.p);
-  }
-  CSE_HIP(hipGetLastError());
-  return CSE_OK;
-}
-
-// ---------------------------------------------------------------------------
-// cse_schur_solve: the reference's conjugate gradients on the device
-// (cg_state.hpp, cg_kernels.hpp)
-// ---------------------------------------------------------------------------
-void cse_cg_default_options(cse_cg_options* o) {
-  if (!o) return;
-  std::memset(o, 0, sizeof(*o));
-  o->min_num_iterations = 1;
-  o->max_num_iterations = 500;
-  o->residual_reset_period = 10;
-  o->check_period = 1;
-  o->r_tolerance = -1.0;
-  o->q_tolerance = 0.0;
-}
-
-extern "C++" {
-namespace {
-
-// The loop of conjugate_gradients_solver.h:108-305 over any operator: `op(x, y)`
-// enqueues y = A x on the stream `s` and returns a cse status; the
-// preconditioner is the one described in `a` (applied inside
-// CgDirectionKernel).  The host enqueues check_period iterations, copies the
-// state to pinned memory, waits once and stops or goes on; it computes no
-// scalar of the iteration.  Nothing is allocated here.
-template <class Op>
-int CgSolve(const cse::CgArgs& a, const cse_cg_options& o, cse::CgState* state_host, hipStream_t s,
-            Op&& op, cse_cg_summary* summary) {
-  int rc;
-  int32_t syncs = 0, enqueued = 0;
-  auto look = [&]() -> int {
-    CSE_HIP(hipMemcpyAsync(state_host, a.state, sizeof(cse::CgState), hipMemcpyDeviceToHost, s));
-    CSE_HIP(hipStreamSynchronize(s));
-    ++syncs;
-    return CSE_OK;
-  };
-  const bool zero_guess = (o.flags & CSE_CG_ZERO_INITIAL_GUESS) != 0;
-  cse::LaunchCgInit(a, zero_guess, s);
-  if (!zero_guess) {
-    if ((rc = op((const double*)a.x, a.tmp))) return rc;
-    cse::LaunchCgInitialResidual(a, s);
-  }
-  CSE_HIP(hipGetLastError());
-  // |b| = 0 and convergence before the first iteration end here.
-  if ((rc = look())) return rc;
-  for (int32_t it = 1; !state_host->done && it <= o.max_num_iterations; ++it) {
-    cse::LaunchCgDirection(a, s);
-    if ((rc = op((const double*)a.p, a.z))) return rc;
-    if (it % o.residual_reset_period == 0) {
-      cse::LaunchCgUpdate(cse::kCgUpdateX, a, s);
-      if ((rc = op((const double*)a.x, a.tmp))) return rc;
-      cse::LaunchCgUpdate(cse::kCgUpdateReset, a, s);
-    } else {
-      cse::LaunchCgUpdate(cse::kCgUpdateFull, a, s);
-    }
-    CSE_HIP(hipGetLastError());
-    ++enqueued;
-    if (enqueued % o.check_period == 0 || it == o.max_num_iterations)
-      if ((rc = look())) return rc;
-  }
-  const cse::CgState& st = *state_host;
-  if (!st.done) return Fail(CSE_ERR_HIP, "cse_schur_solve: the device state did not terminate");
-  summary->termination_type = st.termination_type;
-  summary->reason = st.reason;
-  summary->num_iterations = st.iteration;
-  summary->num_iterations_enqueued = enqueued;
-  summary->num_synchronizations = syncs;
-  summary->reserved = 0;
-  summary->norm_rhs = st.norm_rhs;
-  summary->norm_r = st.norm_r;
-  summary->q = st.Q1;
-  summary->zeta = st.zeta;
-  summary->rho = st.rho;
-  summary->pq = st.pq;
-  return CSE_OK;
-}
-
-}  // namespace
-}  // extern "C++"
-
-int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const double* d_S_values,
-                    const double* d_rhs, double* d_x, double* d_step, cse_cg_summary* summary) {
-  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
-  CSE_SINGLE_DEVICE(ev, "cse_schur_solve");
-  if (!options || !summary || !d_rhs || !d_x)
-    return Fail(CSE_ERR_INVALID, "cse_schur_solve: null options, summary, d_rhs or d_x");
-  const cse_cg_options& o = *options;
-  if (o.check_period < 1) return Fail(CSE_ERR_INVALID, "cse_schur_solve: check_period is below 1");
-  if (o.residual_reset_period < 1)
-    return Fail(CSE_ERR_INVALID, "cse_schur_solve: residual_reset_period is below 1");
-  if (o.max_num_iterations < 1)
-    return Fail(CSE_ERR_INVALID, "cse_schur_solve: max_num_iterations is below 1");
-  if (o.min_num_iterations < 0)
-    return Fail(CSE_ERR_INVALID, "cse_schur_solve: min_num_iterations is negative");
-  if (o.reserved != 0) return Fail(CSE_ERR_INVALID, "cse_schur_solve: options.reserved is not 0");
-  if (o.flags & ~CSE_CG_ZERO_INITIAL_GUESS) return Fail(CSE_ERR_INVALID, "cse_schur_solve: unknown flags");
-  int rc = SchurCheck(ev, true);
-  if (rc) return rc;
-  auto& S = ev->schur;
-  const int64_t n = S.f_cols;
-  if (d_rhs < d_x + n && d_x < d_rhs + n) return Fail(CSE_ERR_INVALID, "cse_schur_solve: d_x overlaps d_rhs");
-  if (d_S_values && !S.sparse.uploaded)
-    return Fail(CSE_ERR_INVALID,
-                "cse_schur_solve: d_S_values without the block-sparse structure "
-                "(cse_schur_complement_sparse_structure, cse_schur_complement_sparse)");
-  auto& W = ev->cg;
-  if ((rc = W.vectors.ensure((size_t)4 * (size_t)std::max<int64_t>(n, 1)))) return rc;
-  if ((rc = W.state.ensure(1))) return rc;
-  if (!W.state_host) CSE_HIP(hipHostMalloc((void**)&W.state_host, sizeof(cse::CgState)));
-  cse::CgArgs a{};
-  a.n = n;
-  a.rhs = d_rhs;
-  a.x = d_x;
-  a.p = W.vectors.p;
-  a.r = a.p + n;
-  a.z = a.r + n;
-  a.tmp = a.z + n;
-  if (S.preconditioner != CSE_SCHUR_IDENTITY) {
-    // The cameras' inverse blocks start at f index f_col_base + 9 lo
-    // (cse_schur_precondition).
-    const Group::GradPlan& P = ev->groups[0].grad[0];
-    a.precond = S.precond.p;
-    a.pre_off = S.f_col_base + 9LL * P.lo;
-    a.pre_n = 9LL * P.count;
-    if (a.pre_off < 0 || a.pre_off + a.pre_n > n || (size_t)(9 * a.pre_n) > S.precond.n)
-      return Fail(CSE_ERR_INVALID, "cse_schur_solve: the preconditioner's blocks do not fit the f columns");
-  }
-  a.state = W.state.p;
-  a.params = cse::CgParams{o.min_num_iterations, o.max_num_iterations, o.r_tolerance, o.q_tolerance};
-  std::memset(summary, 0, sizeof(*summary));
-  if (d_S_values)
-    rc = CgSolve(a, o, W.state_host, ev->stream,
-                 [&](const double* x, double* y) { return cse_schur_explicit_multiply(ev, d_S_values, x, y); },
-                 summary);
-  else
-    rc = CgSolve(a, o, W.state_host, ev->stream,
-                 [&](const double* x, double* y) { return cse_schur_multiply(ev, x, y); }, summary);
-  if (rc) return rc;
-  if (d_step && summary->termination_type != CSE_CG_FAILURE) return cse_schur_back_substitute(ev, d_x, d_step);
-  return CSE_OK;
-}
-
-int cse_schur_complement(cse_evaluator* ev, double* d_S, int64_t ld) {
-  int rc = SchurCheck(ev, true);
-  if (rc) return rc;
-  auto& S = ev->schur;
-  if (!d_S) return Fail(CSE_ERR_INVALID, "null pointer");
-  if (ld < S.f_cols) return Fail(CSE_ERR_INVALID, "cse_schur_complement: ld is smaller than num_cols_f");
-  if ((rc = SchurPairPlanOf(ev, true))) return rc;
-  const auto& Q = S.pairs;
-  hipStream_t s = ev->stream;
-  // Blocks of cameras that share no point stay zero; the rows' padding
-  // [f_cols, ld) is not touched.
-  if (S.f_cols > 0)
-    CSE_HIP(hipMemset2DAsync(d_S, (size_t)ld * sizeof(double), 0, (size_t)S.f_cols * sizeof(double),
-                             (size_t)S.f_cols, s));
-  if (S.D && S.f_cols > 0)
-    hipLaunchKernelGGL(cse::SchurDiagonalFillKernel,
-                       dim3((unsigned)((S.f_cols + cse::kBlockThreads - 1) / cse::kBlockThreads)),
-                       dim3(cse::kBlockThreads), 0, s, S.D, S.e_cols, d_S, ld, S.f_cols);
-  cse::SchurPairArgs a = MakeSchurPairArgs(ev);
-  a.S = d_S;
-  a.ld = ld;
-  if (Q.num_chunks > 0) {
-    hipLaunchKernelGGL((cse::SchurPairChunkKernel<9>),
-                       dim3((unsigned)((Q.num_chunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
-                       dim3(cse::kBlockThreads), 0, s, a);
-    const int64_t entries = Q.num_blocks * cse::kSchurBlockDoubles;
-    hipLaunchKernelGGL((cse::SchurPairFinishKernel<9>),
-                       dim3((unsigned)((entries + cse::kBlockThreads - 1) / cse::kBlockThreads)),
-                       dim3(cse::kBlockThreads), 0, s, a);
-  }
-  CSE_HIP(hipGetLastError());
-  return CSE_OK;
-}
-
 int cse_plus_device(cse_evaluator* ev, const double* d_state, const double* d_delta,
                     double* d_state_plus_delta) {
   if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
@@ -2055,10 +1096,3 @@ int cse_reset_kernel_stats(cse_evaluator* ev) {
 }
 
 }  // extern "C"
-
-// The asan build keeps the per-block loss kernels in this object (its link
-// line, tests/cpp/Makefile, lists the objects of ABI 5).
-#ifdef CSE_PER_BLOCK_LOSS_IN_THIS_TU
-#include "per_block_loss_kernels.hip"
-#include "cg_kernels.hip"  // with this unit's flags there: no sanitizer run reaches an infinite scalar
-#endif

@@ -4,7 +4,7 @@
 // layout policy, gather) to a launch function.  Host code, templates only:
 // cse_evaluator.hip instantiates the pickers with UniformLosses and
 // per_block_loss_kernels.hip with PerBlockLosses, each TU compiling the
-// kernels its pickers name.
+// kernels its pickers name; linear_operators.hip takes VisitKind alone.
 #ifndef CSE_KERNEL_PICKERS_HPP_
 #define CSE_KERNEL_PICKERS_HPP_
 
@@ -15,7 +15,7 @@
 
 #include "../../include/cse.h"
 #include "group_store_kernel.hpp"
-#include "launch_eval.hpp"
+#include "launch.hpp"
 #include "plan.hpp"
 
 namespace cse {

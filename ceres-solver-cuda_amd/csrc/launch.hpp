@@ -1,7 +1,8 @@
 // launch.hpp -- host-side launches of the evaluator kernels for one functor
 // kind, in their shipped settings (grid, workgroup size, tuning struct).
 //
-// Shared by the library (cse_evaluator.hip) and by user functor kinds, whose
+// Shared by the library (cse_evaluator.hip, linear_operators.hip and the
+// kernel TUs through kernel_pickers.hpp) and by user functor kinds, whose
 // kernels are instantiated in the user's hipcc TU
 // (include/ceres_amd/autodiff_cuda.h) the way the reference instantiates
 // EvaluateKernel<CostFunctor, LossFunctionCUDA, kR, Ns...> in the user's nvcc
@@ -10,17 +11,85 @@
 // exactly the kernel the library launches for the same (kind, loss, layout,
 // outputs); the Snavely camera's specialised kernels (group store, fused
 // gradient, held cameras) are chosen in cse_evaluator.hip and never reach
-// these.  The launches of the evaluation kernels themselves are in
-// launch_eval.hpp (TUs that instantiate only those include it alone).
+// these.  Templates only: a TU compiles the kernels of the launches it
+// instantiates and no others.
 #ifndef CSE_LAUNCH_HPP_
 #define CSE_LAUNCH_HPP_
 
 #include <hip/hip_runtime.h>
 
-#include "launch_eval.hpp"
+#include "evaluate_kernel.hpp"
 #include "operator_kernels.hpp"
 
 namespace cse {
+
+inline int64_t Chunks(int64_t n) { return (n + kWave - 1) / kWave; }
+
+// The general kernel: one residual block per lane, offsets through the
+// descriptor's tables (EvaluateTableKernel).
+template <class K, int L, bool J>
+void LaunchTableKernel(const GroupArgs& a, int64_t num_wg, hipStream_t s) {
+  hipLaunchKernelGGL((EvaluateTableKernel<K, L, J>), dim3((unsigned)num_wg), dim3(kBlockThreads), 0, s,
+                     a);
+}
+
+// The affine kernel: one 64-block chunk per wave, 4 waves per workgroup.
+// kCoop 2: slot 0 by LDS-DMA from the repacked table; 1: 8-byte pieces from
+// the state.
+template <class K, int L, bool J, bool Crs, int kCoop, class T = ShippedTune>
+void LaunchAffineChunks(const GroupArgs& a, int64_t num_wg, hipStream_t s) {
+  hipLaunchKernelGGL((EvaluateAffineChunks<K, L, J, Crs, kCoop, T>), dim3((unsigned)num_wg),
+                     dim3(kBlockThreads), 0, s, a);
+}
+
+// The residual+Jacobian evaluation of two-slot kinds with the LDS-DMA
+// gather: two half-wave staging rounds, one wave per workgroup
+// (BlockSparseMatrix: EvaluateAffineChunksTwoRoundW1; CompressedRow:
+// EvaluateAffineChunksTwoRoundCrsW1).
+template <class K, int L, int kCoop, class T = ShippedTune>
+void LaunchTwoRoundW1(const GroupArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((EvaluateAffineChunksTwoRoundW1<K, L, kCoop, T>), dim3((unsigned)Chunks(a.n)),
+                     dim3(kWave), 0, s, a);
+}
+template <class K, int L, int kCoop, class T = ShippedTune>
+void LaunchTwoRoundCrsW1(const GroupArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((EvaluateAffineChunksTwoRoundCrsW1<K, L, kCoop, T>), dim3((unsigned)Chunks(a.n)),
+                     dim3(kWave), 0, s, a);
+}
+
+// The affine evaluation of a (non-Snavely) kind: the kernel the library's
+// Pick chooses for (layout, outputs, gather).
+template <class K, int L, bool Crs, bool J, bool kDma>
+void LaunchAffine(const GroupArgs& a, int64_t num_wg, hipStream_t s) {
+  if constexpr (J && kDma && !Crs && kTwoRoundBsm<K>) {
+    LaunchTwoRoundW1<K, L, 2>(a, s);
+  } else if constexpr (J && kDma && Crs) {
+    LaunchTwoRoundCrsW1<K, L, 2>(a, s);
+  } else {
+    LaunchAffineChunks<K, L, J, Crs, kDma ? 2 : 1>(a, num_wg, s);
+  }
+}
+
+// The fused gradient (gradient_mode 0) of a two-slot kind whose slot 1 has
+// 3 parameters, the form the library's Snavely kinds take: the Jacobian
+// kernel that also sums the slot-1 rows of its sorted blocks
+// (EvaluateAffineChunksFusedPointsW1, one wave per workgroup), and the
+// slot-0 rows by re-evaluation in slot-0 order (CameraGradientKernel).
+template <class K>
+constexpr bool kFusedGradShape = KindTraits<K>::NB == 2 && KindTraits<K>::S1 == 3;
+
+template <class K, int L, bool Crs>
+void LaunchFusedPointsKernel(const GroupArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((EvaluateAffineChunksFusedPointsW1<K, L, Crs>), dim3((unsigned)Chunks(a.n)), dim3(kWave),
+                     0, s, a);
+}
+
+template <class K, int L>
+void LaunchCameraGradient(const CamGradArgs& g, int64_t nslots, hipStream_t s) {
+  constexpr int W = kWavesPerBlock;
+  hipLaunchKernelGGL((CameraGradientKernel<K, L, W>), dim3((unsigned)((nslots + W - 1) / W)), dim3(W * kWave), 0,
+                     s, g);
+}
 
 // J x (affine or table) and J^T x (table; affine groups use the gradient
 // post-pass for it).  which: 0 = J x affine, 1 = J x table, 2 = J^T x table.

@@ -28,6 +28,10 @@
 //     back substitution (BackSubstitute, :216-238):  z_b = b_b - F_b x_c,
 //          y_p = w_p, no f-block sum.
 // All sums run in a fixed order: results are bit-identical run to run.
+//
+// linear_operators.hip owns the plain (non-template) kernels here
+// (SchurDiagKernel, AxpyKernel and CGNR's DtDxpyKernel): no other TU of the
+// library includes this.
 #ifndef CSE_SCHUR_KERNELS_HPP_
 #define CSE_SCHUR_KERNELS_HPP_
 
@@ -473,6 +477,13 @@ __global__ __launch_bounds__(kBlockThreads) void SchurDiagKernel(const double* D
 __global__ __launch_bounds__(kBlockThreads) void AxpyKernel(const double* x, double* y, int64_t n) {
   const int64_t k = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x;
   if (k < n) y[k] += x[k];
+}
+
+// y += D .* D .* x (CudaVector::DtDxpy, cgnr_solver.cc:236): cse_cgnr_multiply's.
+__global__ __launch_bounds__(kBlockThreads) void DtDxpyKernel(const double* D, const double* x,
+                                                              double* y, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x;
+  if (i < n) y[i] += D[i] * D[i] * x[i];
 }
 
 // The init's camera-order pass, one wave per block list chunk (the camera

@@ -3,19 +3,24 @@
 
   tools/isa_diff.py OLD_DIR NEW_DIR [--per-block]
 
-OLD_DIR and NEW_DIR are build/isa directories (cse_evaluator.s and
-resource_usage.txt).  For every kernel in both: is the instruction stream the
+OLD_DIR and NEW_DIR are build/isa directories: every *.s and every
+*resource_usage.txt in each is read, so a kernel that moved from one TU to
+another still matches by symbol.  A symbol that two files of one directory
+define is reported.  For every kernel in both: is the instruction stream the
 same (labels renumbered, comments and directives dropped), and are the
 register, LDS, scratch and occupancy figures the same?  Kernels that differ
 are listed with the number of changed lines and whether every changed line is
 a kernel-argument load (s_load_* from the kernarg pointer: what a grown
-argument struct moves).
+argument struct moves).  Symbols of one directory alone are listed with their
+file.
 
---per-block: also read NEW_DIR/per_block_resource_usage.txt and list each
-per-block loss kernel whose figures differ from its uniform twin's (loss
+--per-block: also list each per-block loss kernel (NEW_DIR/per_block*
+resource_usage.txt) whose figures differ from its uniform twin's (loss
 template argument L - 4) in occupancy, scratch or spills.
 """
 import difflib
+import glob
+import os
 import re
 import sys
 
@@ -50,13 +55,35 @@ def short(r):
             f"occ {r.get('Occupancy [waves/SIMD]')}")
 
 
+def read_dir(d):
+    """Every symbol's body, file and resource figures over the directory's files."""
+    body, where, res = {}, {}, {}
+    for path in sorted(glob.glob(d + "/*.s")):
+        for k, v in bodies(path).items():
+            where.setdefault(k, []).append(os.path.basename(path))
+            body[k] = v
+    for path in sorted(glob.glob(d + "/*resource_usage.txt")):
+        res.update(resources(path))
+    for k, files in sorted(where.items()):
+        if len(files) > 1:
+            print(f"DUPLICATE {k} in {d}: {' '.join(files)}")
+    return body, where, res
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     old, new = args[0].rstrip("/"), args[1].rstrip("/")
-    a, b = bodies(old + "/cse_evaluator.s"), bodies(new + "/cse_evaluator.s")
-    ra, rb = resources(old + "/resource_usage.txt"), resources(new + "/resource_usage.txt")
-    print(f"kernels: old {len(a)}, new {len(b)}; only old {sorted(set(a) - set(b))}; "
-          f"only new {sorted(set(b) - set(a))}")
+    (a, wa, ra), (b, wb, rb) = read_dir(old), read_dir(new)
+    print(f"kernels: old {len(a)}, new {len(b)}; only old {len(set(a) - set(b))}, "
+          f"only new {len(set(b) - set(a))}")
+    for k in sorted(set(a) - set(b)):
+        print(f"ONLY OLD {wa[k][0]} {k}")
+    for k in sorted(set(b) - set(a)):
+        print(f"ONLY NEW {wb[k][0]} {k}")
+    moved = sorted(k for k in set(a) & set(b) if wa[k] != wb[k])
+    print(f"in another file than before: {len(moved)}")
+    for k in moved:
+        print(f"MOVED {wa[k][0]} -> {wb[k][0]} {k}")
     same = 0
     for k in sorted(set(a) & set(b)):
         if a[k] == b[k] and ra.get(k) == rb.get(k):
@@ -71,7 +98,9 @@ def main():
             print(f"     old {short(ra.get(k, {}))}\n     new {short(rb.get(k, {}))}")
     print(f"identical instruction stream and resource figures: {same} of {len(set(a) & set(b))}")
     if "--per-block" in sys.argv:
-        rp = resources(new + "/per_block_resource_usage.txt")
+        rp = {}
+        for path in glob.glob(new + "/per_block*resource_usage.txt"):
+            rp.update(resources(path))
         twin = lambda k: re.sub(r"ELi([456])E", lambda m: "ELi%dE" % (int(m.group(1)) - 4), k, count=1)
         keys = ("Occupancy [waves/SIMD]", "ScratchSize [bytes/lane]", "VGPRs Spill")
         n = 0

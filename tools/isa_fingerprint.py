@@ -23,6 +23,16 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, "ceres-solver-cuda_amd")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-signed-zeros", "-ffinite-math-only",
          "-munsafe-fp-atomics", "-w", "--cuda-device-only", "-S"]
+# The library's kernel-bearing TUs (the Makefile's ISA_TUS).
+KERNEL_TUS = ["csrc/cse_evaluator.hip", "csrc/linear_operators.hip", "csrc/jet_kernels.hip",
+              "csrc/per_block_loss_kernels.hip", "csrc/cg_kernels.hip"]
+
+
+def flags_of(src):
+    """The Makefile's flags for the TU: cg_kernels.hip is built without the two finite-math flags."""
+    if os.path.basename(src) == "cg_kernels.hip":
+        return [f for f in FLAGS if f not in ("-fno-signed-zeros", "-ffinite-math-only")]
+    return FLAGS
 
 
 def functions(asm):
@@ -45,11 +55,11 @@ def functions(asm):
 
 
 def main():
-    srcs = sys.argv[1:] or ["csrc/cse_evaluator.hip", "csrc/jet_kernels.hip", "csrc/multi_device.hip"]
+    srcs = sys.argv[1:] or KERNEL_TUS
     names = []
     with tempfile.TemporaryDirectory() as td:
         outs = [os.path.join(td, "k%d.s" % i) for i in range(len(srcs))]
-        procs = [subprocess.Popen(["/opt/rocm/bin/hipcc"] + FLAGS + ["-o", o, os.path.join(PKG, s)],
+        procs = [subprocess.Popen(["/opt/rocm/bin/hipcc"] + flags_of(s) + ["-o", o, os.path.join(PKG, s)],
                                   cwd=PKG) for s, o in zip(srcs, outs)]
         if any(p.wait() for p in procs):
             sys.exit("compile failed")
