@@ -185,6 +185,8 @@ SIGNATURES = {
     "cse_jacobian_right_multiply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cse_jacobian_left_multiply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cse_cgnr_multiply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cse_jacobian_squared_column_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cse_jacobian_scale_columns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cse_schur_structure": (C.c_int, [C.c_void_p, P_i64, P_i64]),
     "cse_schur_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int]),

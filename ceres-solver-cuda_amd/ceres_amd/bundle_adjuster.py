@@ -90,6 +90,14 @@ def parse(argv=None):
                          "measured at 49 cameras; 16 already loses to the trailing iterations), 1 "
                          "from about a thousand cameras on, where a product is long against a host "
                          "wait; DESIGN 3.6c")
+    ap.add_argument("--jacobi_scaling", action="store_true",
+                    help="Solver::Options::jacobi_scaling (on by default in the reference, off here so "
+                         "that earlier runs keep their iterates): at iteration 0 scaling = 1 / (1 + "
+                         "sqrt(squared column norm)) (cse_jacobian_squared_column_norm), every Jacobian "
+                         "is scaled in place (cse_jacobian_scale_columns), the LM diagonal is the norm "
+                         "of the scaled Jacobian clamped to [1e-6, 1e32], the linear solver runs on the "
+                         "scaled Jacobian and the step is un-scaled for Plus "
+                         "(trust_region_minimizer.cc:259-275, 443-446)")
     args = ap.parse_args(argv)
     if args.use_explicit_schur_complement and args.linear_solver != "iterative_schur":
         raise SystemExit("--use_explicit_schur_complement needs --linear_solver iterative_schur, not "
@@ -134,7 +142,10 @@ def cholesky_solve(S, rhs):
         return torch.from_numpy(np.linalg.solve(c.T, y)).to(S.device)
 
 
-def solve(args):
+def solve(args, stats=None):
+    """stats (a dict, optional) receives "lm_diagonal": the (min, max) of every
+    LM diagonal before its clamp, in the order they were taken, and with
+    --jacobi_scaling "jacobi_scaling": the scaling's (min, max)."""
     import torch
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -332,9 +343,29 @@ def solve(args):
         ev.schur_back_substitute_device(xf.data_ptr(), dx.data_ptr())
         return dx, 0
 
+    # Solver::Options::jacobi_scaling (trust_region_minimizer.cc:259-275): the
+    # scaling comes from the first Jacobian and every Jacobian is scaled in
+    # place; the solvers, the LM diagonal and the model then live in the scaled
+    # space (g holds the scaled gradient J_s^T r = scaling .* J^T r).
+    scaling = None
+
+    def scale_jacobian():
+        nonlocal scaling
+        if scaling is None:
+            scaling = torch.empty(n, dtype=f64, device=dev)
+            ev.squared_column_norm_device(jac.data_ptr(), scaling.data_ptr())
+            scaling = 1.0 / (1.0 + torch.sqrt(scaling))
+            if stats is not None:
+                stats["jacobi_scaling"] = (float(scaling.min().item()), float(scaling.max().item()))
+        ev.scale_columns_device(jac.data_ptr(), scaling.data_ptr())
+        if not grad_from_init:
+            g.mul_(scaling)
+
     status = timed("Jacobian & residual evaluation", jacobian_eval)
     if status != 0:
         raise SystemExit("initial evaluation failed")
+    if args.jacobi_scaling:
+        timed("Jacobi scaling", scale_jacobian)
     initial_cost = float(cost.item())
     radius = args.initial_trust_region_radius
     # LevenbergMarquardtStrategy (levenberg_marquardt_strategy.cc:157-170):
@@ -351,18 +382,32 @@ def solve(args):
     for it in range(args.num_iterations):
         # Jacobi scaling: diag(J^T J) = column sums of squared values, one
         # left-multiply of the squared Jacobian with a vector of ones.
-        if d_stale:
+        if d_stale and args.jacobi_scaling:
+            # LevenbergMarquardtStrategy::ComputeStep (levenberg_marquardt_strategy.cc:
+            # 78-94): the squared column norms of the (scaled) Jacobian, clamped to
+            # [min_lm_diagonal, max_lm_diagonal].
+            timed("LM diagonal", lambda: ev.squared_column_norm_device(jac.data_ptr(), D.data_ptr()))
+            if stats is not None:
+                stats.setdefault("lm_diagonal", []).append((float(D.min().item()), float(D.max().item())))
+            D.clamp_(min=1e-6, max=1e32)
+            d_stale = False
+        elif d_stale:
             if jac2 is None:
                 jac2 = torch.empty_like(jac)
             torch.mul(jac, jac, out=jac2)
             D.zero_()
             ev.left_multiply_device(jac2.data_ptr(), ones.data_ptr(), D.data_ptr())
+            if stats is not None:
+                stats.setdefault("lm_diagonal", []).append((float(D.min().item()), float(D.max().item())))
             D.clamp_(min=1e-6)
             d_stale = False
         solver = {"iterative_schur": schur_solve, "dense_schur": dense_schur_solve,
                   "cgnr": cgnr}[args.linear_solver]
         dx, cg_iters = timed("Linear solver", lambda: solver(1.0 / radius))
-        timed("Plus", lambda: ev.plus_device(x.data_ptr(), dx.data_ptr(), cand.data_ptr()))
+        # dx is the step of the (scaled) linear system; Plus takes delta =
+        # step .* scaling (trust_region_minimizer.cc:443-446).
+        delta = dx * scaling if args.jacobi_scaling else dx
+        timed("Plus", lambda: ev.plus_device(x.data_ptr(), delta.data_ptr(), cand.data_ptr()))
 
         def cand_eval():
             ev.evaluate_device(cand.data_ptr(), ccost.data_ptr(), None, None, None)
@@ -379,12 +424,16 @@ def solve(args):
         # TrustRegionMinimizer::IsStepSuccessful: relative decrease above
         # min_relative_decrease (trust_region_minimizer.cc).
         accepted = ok and rho > min_relative_decrease
-        rows.append((it, old_cost, new_cost, float(g.norm().item()), float(dx.norm().item()),
+        # The table shows the unscaled gradient and the step Plus took.
+        gnorm = float((g / scaling).norm().item()) if args.jacobi_scaling else float(g.norm().item())
+        rows.append((it, old_cost, new_cost, gnorm, float(delta.norm().item()),
                      radius, cg_iters, accepted))
         if accepted:
             x.copy_(cand)
             if timed("Jacobian & residual evaluation", lambda: jacobian_eval(False)) != 0:
                 raise SystemExit(f"iteration {it}: Jacobian evaluation at the accepted point failed")
+            if args.jacobi_scaling:
+                timed("Jacobi scaling", scale_jacobian)
             d_stale = True
             radius = min(max_radius, radius / max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3))
             decrease_factor = 2.0
@@ -401,8 +450,8 @@ def solve(args):
     return initial_cost, float(cost.item()), rows
 
 
-def main(argv=None):
-    return solve(parse(argv))
+def main(argv=None, stats=None):
+    return solve(parse(argv), stats)
 
 
 if __name__ == "__main__":

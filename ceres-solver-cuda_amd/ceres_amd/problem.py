@@ -677,6 +677,19 @@ class Evaluator:
         return _cse.check(_cse.lib().cse_cgnr_multiply(self.handle, d_jacobian, d_D, d_x, d_y),
                           "cse_cgnr_multiply")
 
+    def squared_column_norm_device(self, d_jacobian, d_out):
+        """out[c] = sum over rows of J[r][c]^2 on the device, num_effective_parameters
+        entries, assigned (SparseMatrix::SquaredColumnNorm); bit-identical repeats on
+        the affine path."""
+        return _cse.check(_cse.lib().cse_jacobian_squared_column_norm(self.handle, d_jacobian, d_out),
+                          "cse_jacobian_squared_column_norm")
+
+    def scale_columns_device(self, d_jacobian, d_scale):
+        """J[r][c] *= scale[c] in place on the device (SparseMatrix::ScaleColumns);
+        every stored value becomes exactly value * scale[column]."""
+        return _cse.check(_cse.lib().cse_jacobian_scale_columns(self.handle, d_jacobian, d_scale),
+                          "cse_jacobian_scale_columns")
+
     # ---- ITERATIVE_SCHUR (ImplicitSchurComplement on the device) ----------
     def schur_structure(self):
         """(num_cols_e, num_cols_f) of the Schur split; raises if the problem

@@ -1,6 +1,7 @@
 // linear_operators.hip -- the calls of the C ABI (include/cse.h) that a linear
 // solver makes on the evaluator (evaluator.hpp): J x, J^T x and CGNR
-// (operator_kernels.hpp), the implicit Schur complement (schur_kernels.hpp),
+// (operator_kernels.hpp), the column norms and ScaleColumns
+// (column_kernels.hpp), the implicit Schur complement (schur_kernels.hpp),
 // the explicit one (schur_complement_kernels.hpp) and cse_schur_solve
 // (cg_kernels.h).  The gradient post-pass kernels are launched through
 // evaluator.hpp's functions: they stay instantiated in cse_evaluator.hip.
@@ -9,6 +10,7 @@
 #include <new>
 
 #include "cg_kernels.h"
+#include "column_kernels.hpp"
 #include "evaluator.hpp"
 #include "kernel_pickers.hpp"
 #include "schur_complement_kernels.hpp"
@@ -64,6 +66,143 @@ int JacobianMultiply(cse_evaluator* ev, const double* J, const double* x, double
     CSE_HIP(hipGetLastError());
   }
   return CSE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// SquaredColumnNorm and ScaleColumns (column_kernels.hpp, operator_kernels.hpp)
+// ---------------------------------------------------------------------------
+// The norm of slot j through its gradient plan, in the plan's form (as
+// LaunchGradientSlot): identity order = contiguous block ranges; chunks of at
+// most kGradChunk blocks and the ordered chunk reduce; one lane per parameter
+// block.  P.chunk_partial is the plan's own (nchunks x S).
+template <int NR, int S>
+void LaunchColumnNormSlot(const cse::GradArgs& ga, const Group::GradPlan& P, hipStream_t s) {
+  if (ga.count <= 0) return;
+  if (ga.perm == nullptr) {
+    hipLaunchKernelGGL((cse::ColumnNormRangeKernel<NR, S>), dim3((unsigned)((ga.count + cse::kWave - 1) / cse::kWave)),
+                       dim3(cse::kWave), 0, s, ga);
+  } else if (P.wave) {
+    const cse::GradChunks ch{P.chunk_begin.p, P.chunk_off.p, P.chunk_partial.p, P.nchunks};
+    if (P.nchunks > 0)
+      hipLaunchKernelGGL((cse::ColumnNormLanesKernel<NR, S>),
+                         dim3((unsigned)((P.nchunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
+                         dim3(cse::kBlockThreads), 0, s, ga, ch);
+    hipLaunchKernelGGL((cse::ColumnNormChunkReduceKernel<S>),
+                       dim3((unsigned)((ga.count + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                       dim3(cse::kBlockThreads), 0, s, ga, ch);
+  } else {
+    hipLaunchKernelGGL((cse::ColumnNormSlotKernel<NR, S>),
+                       dim3((unsigned)((ga.count + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                       dim3(cse::kBlockThreads), 0, s, ga);
+  }
+}
+
+// Every shape an affine group can have (DetectAffine: at most 3 residuals)
+// with blocks of up to 10 columns; false for a larger block.
+template <int NR>
+bool LaunchColumnNormSize(int size, const cse::GradArgs& ga, const Group::GradPlan& P, hipStream_t s) {
+  switch (size) {
+    case 1: LaunchColumnNormSlot<NR, 1>(ga, P, s); return true;
+    case 2: LaunchColumnNormSlot<NR, 2>(ga, P, s); return true;
+    case 3: LaunchColumnNormSlot<NR, 3>(ga, P, s); return true;
+    case 4: LaunchColumnNormSlot<NR, 4>(ga, P, s); return true;
+    case 5: LaunchColumnNormSlot<NR, 5>(ga, P, s); return true;
+    case 6: LaunchColumnNormSlot<NR, 6>(ga, P, s); return true;
+    case 7: LaunchColumnNormSlot<NR, 7>(ga, P, s); return true;
+    case 8: LaunchColumnNormSlot<NR, 8>(ga, P, s); return true;
+    case 9: LaunchColumnNormSlot<NR, 9>(ga, P, s); return true;
+    case 10: LaunchColumnNormSlot<NR, 10>(ga, P, s); return true;
+    default: return false;
+  }
+}
+
+bool ColumnNormShape(int nr, int size) { return nr >= 1 && nr <= 3 && size >= 1 && size <= 10; }
+
+void LaunchColumnNormPass(int nr, int size, const cse::GradArgs& ga, const Group::GradPlan& P, hipStream_t s) {
+  if (nr == 1) LaunchColumnNormSize<1>(size, ga, P, s);
+  if (nr == 2) LaunchColumnNormSize<2>(size, ga, P, s);
+  if (nr == 3) LaunchColumnNormSize<3>(size, ga, P, s);
+}
+
+// The block-per-lane kernels' arguments: table addressing, or the affine
+// parameters of a group whose tables were not uploaded.
+cse::ColumnBlockArgs MakeColumnBlockArgs(cse_evaluator* ev, const Group& G, bool affine) {
+  cse::ColumnBlockArgs a{};
+  a.n = G.n;
+  a.ids = G.ids.p;
+  a.nr = G.shape.nr;
+  a.nb = G.shape.nb;
+  for (int j = 0; j < cse::kMaxSlots; ++j) a.sz[j] = G.shape.sz[j];
+  a.affine = affine ? 1 : 0;
+  a.pbs = ev->pbs.p;
+  a.gindex = G.gindex.p;
+  a.first = G.first;
+  a.jac_layout = ev->jac_layout.p;
+  a.jac_offsets = ev->jac_offsets.p;
+  if (affine) {
+    // The Jacobian's columns of slot 0 (s0) are the tangent's on a manifold kind.
+    a.sz[0] = G.shape.s0;
+    a.sz[1] = G.shape.s1;
+    for (int j = 0; j < 2; ++j) {
+      a.delta_base[j] = G.delta_base[j];
+      a.jac_stride[j] = G.jac_stride[j];
+      for (int r = 0; r < 3; ++r) a.jac_base[j][r] = G.jac_base[j][r];
+    }
+  }
+  return a;
+}
+
+template <bool kScale>
+void LaunchColumnBlocks(const cse::ColumnBlockArgs& a, double* jac, const double* scale, double* out,
+                        hipStream_t s) {
+  hipLaunchKernelGGL((cse::ColumnBlockKernel<kScale>),
+                     dim3((unsigned)((a.n + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                     dim3(cse::kBlockThreads), 0, s, a, jac, scale, out);
+}
+
+int ColumnOpCheck(cse_evaluator* ev, const char* what, const void* p0, const void* p1) {
+  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
+  CSE_SINGLE_DEVICE(ev, what);
+  if (!ev->has_layout) return Fail(CSE_ERR_INVALID, "the descriptor had no Jacobian layout");
+  if (!p0 || !p1) return Fail(CSE_ERR_INVALID, "null pointer");
+  CSE_HIP(hipSetDevice(ev->device));
+  return CSE_OK;
+}
+
+// The chunk runs of an affine group without held cameras (ScaleStreamArgs).
+cse::ScaleStreamArgs MakeScaleStreamArgs(const Group& G) {
+  const int nr = G.shape.nr, nb = G.shape.nb;
+  const int sz[2] = {G.shape.s0, nb > 1 ? G.shape.s1 : 0};
+  cse::ScaleStreamArgs a{};
+  a.n = G.n;
+  a.ids = G.ids.p;
+  a.nb = nb;
+  a.ntab = sz[0] + sz[1];
+  for (int j = 0; j < nb; ++j) {
+    a.sz[j] = sz[j];
+    a.delta_base[j] = G.delta_base[j];
+  }
+  if (G.policy == cse::kAffineCrs) {
+    // Rows of ntab doubles from row0; each slot at its column of the row.
+    int64_t row0 = G.jac_base[0][0];
+    for (int j = 0; j < nb; ++j) row0 = std::min(row0, G.jac_base[j][0]);
+    for (int j = 0; j < nb; ++j) a.tab_off[j] = (int)(G.jac_base[j][0] - row0);
+    a.nruns = 1;
+    a.run_base[0] = row0;
+    a.run_cell[0] = nr * a.ntab;
+    a.run_s[0] = a.ntab;
+    a.run_tab[0] = 0;
+  } else {
+    a.nruns = nb;
+    for (int j = 0; j < nb; ++j) {
+      a.tab_off[j] = j == 0 ? 0 : sz[0];
+      a.run_base[j] = G.jac_base[j][0];
+      a.run_cell[j] = nr * sz[j];
+      a.run_s[j] = sz[j];
+      a.run_tab[j] = a.tab_off[j];
+    }
+  }
+  return a;
 }
 
 // ---------------------------------------------------------------------------
@@ -479,6 +618,60 @@ int cse_cgnr_multiply(cse_evaluator* ev, const double* d_jacobian_values, const 
                          dim3(W * cse::kWave), 0, s, a, d_x, d_y);
     CSE_HIP(hipGetLastError());
     if ((rc = LaunchFusedGradTail(G, d_y, s))) return rc;
+  }
+  return CSE_OK;
+}
+
+int cse_jacobian_squared_column_norm(cse_evaluator* ev, const double* d_jacobian_values, double* d_x) {
+  int rc = ColumnOpCheck(ev, "cse_jacobian_squared_column_norm", d_jacobian_values, d_x);
+  if (rc) return rc;
+  hipStream_t s = ev->stream;
+  // Assigned: zero, then every group adds (groups may share columns, and a
+  // column without cells reads 0).
+  if (ev->num_effective > 0) CSE_HIP(hipMemsetAsync(d_x, 0, ev->num_effective * sizeof(double), s));
+  for (auto& G : ev->groups) {
+    if (G.n == 0) continue;
+    // Held cameras (const0): the table kernel, as the products.
+    const bool affine = G.affine && !G.const0;
+    const int sizes[2] = {G.shape.s0, G.shape.s1};
+    bool plans = affine;
+    for (int j = 0; j < G.shape.nb; ++j)
+      plans = plans && G.grad[j].ready && ColumnNormShape(G.shape.nr, sizes[j]) &&
+              (G.grad[j].sorted || !G.grad[j].wave || G.grad[j].chunk_partial.p);
+    if (plans) {
+      for (int j = 0; j < G.shape.nb; ++j)
+        LaunchColumnNormPass(G.shape.nr, sizes[j], SlotGradArgs(G, j, d_jacobian_values, nullptr, d_x),
+                             G.grad[j], s);
+    } else {
+      if (!affine && !ev->any_general)
+        return Fail(CSE_ERR_UNSUPPORTED, "table-path tables were not uploaded");
+      LaunchColumnBlocks<false>(MakeColumnBlockArgs(ev, G, affine), const_cast<double*>(d_jacobian_values),
+                                nullptr, d_x, s);
+    }
+    CSE_HIP(hipGetLastError());
+  }
+  return CSE_OK;
+}
+
+int cse_jacobian_scale_columns(cse_evaluator* ev, double* d_jacobian_values, const double* d_scale) {
+  int rc = ColumnOpCheck(ev, "cse_jacobian_scale_columns", d_jacobian_values, d_scale);
+  if (rc) return rc;
+  hipStream_t s = ev->stream;
+  for (auto& G : ev->groups) {
+    if (G.n == 0) continue;
+    if (G.affine && !G.const0) {
+      const cse::ScaleStreamArgs a = MakeScaleStreamArgs(G);
+      constexpr int W = kOperatorWavesPerWg;
+      const int64_t chunks = (G.n + cse::kWave - 1) / cse::kWave;
+      hipLaunchKernelGGL((cse::ScaleColumnsStreamKernel<W>), dim3((unsigned)((chunks + W - 1) / W)),
+                         dim3(W * cse::kWave), (size_t)W * cse::kWave * a.ntab * sizeof(double), s, a,
+                         d_jacobian_values, d_scale);
+    } else {
+      // Held cameras (compacted F cells, two row widths) and the table path.
+      if (!ev->any_general) return Fail(CSE_ERR_UNSUPPORTED, "table-path tables were not uploaded");
+      LaunchColumnBlocks<true>(MakeColumnBlockArgs(ev, G, false), d_jacobian_values, d_scale, nullptr, s);
+    }
+    CSE_HIP(hipGetLastError());
   }
   return CSE_OK;
 }

@@ -549,6 +549,127 @@ __global__ __launch_bounds__(kWPB * kWave) void CgnrMultiplyKernel(const GroupAr
   }
 }
 
+// ---------------------------------------------------------------------------
+// Squared column norms (cse_jacobian_squared_column_norm) of an affine group:
+// x[c] += sum over the rows of J[r][c]^2, slot by slot through the gradient
+// plan, in the three forms of the gradient post-pass (GradientRangeKernel,
+// GradientLanesKernel + the ordered chunk reduce, GradientSlotKernel) with
+// row[c] * row[c] in place of row[c] * r[k]: no residual is read, and each
+// slot reads only its own cells.  g.res is unused; g.grad is the output,
+// zero-filled by the host before the first group.
+// ---------------------------------------------------------------------------
+template <int NR, int S>
+__global__ __launch_bounds__(kWave) void ColumnNormRangeKernel(const GradArgs g) {
+  constexpr int E = NR * S;
+  constexpr int T = kWave;  // blocks per tile
+  __shared__ double prod[T * E];
+  const int lane = threadIdx.x;
+  const int64_t p0 = (int64_t)blockIdx.x * kWave;
+  const int64_t p = p0 + lane;
+  const int64_t pend = p0 + kWave < g.count ? p0 + kWave : g.count;
+  const int64_t B0 = g.off[p0], B1 = g.off[pend];
+  const int64_t my0 = p < g.count ? g.off[p] : B1, my1 = p < g.count ? g.off[p + 1] : B1;
+  double acc[S];
+#pragma unroll
+  for (int cc = 0; cc < S; ++cc) acc[cc] = 0.0;
+  for (int64_t t0 = B0; t0 < B1; t0 += T) {
+    const int nb = B1 - t0 < T ? (int)(B1 - t0) : T;
+#pragma unroll
+    for (int it = 0; it < E; ++it) {
+      const int t = it * kWave + lane;  // element t of the tile
+      const int bm = t / E, e = t - bm * E, k = e / S, cc = e - k * S;
+      double v = 0.0;
+      if (bm < nb) v = g.jac[g.jrow[k] + g.jstride * (t0 + bm) + cc];
+      prod[t] = v * v;
+    }
+    __syncthreads();
+    const int64_t lo = my0 > t0 ? my0 : t0, hi = my1 < t0 + nb ? my1 : t0 + nb;
+    for (int64_t b = lo; b < hi; ++b) {
+      const int bm = (int)(b - t0);
+#pragma unroll
+      for (int k = 0; k < NR; ++k)
+#pragma unroll
+        for (int cc = 0; cc < S; ++cc) acc[cc] += prod[bm * E + k * S + cc];
+    }
+    __syncthreads();
+  }
+  if (p < g.count) {
+    double* dst = g.grad + g.delta_base + (int64_t)S * (g.lo + p);
+#pragma unroll
+    for (int cc = 0; cc < S; ++cc) dst[cc] += acc[cc];
+  }
+}
+
+// One wave per chunk of at most kGradChunk blocks of one parameter block:
+// lane per block, S sums per lane, a fixed xor-butterfly, the chunk's partial.
+template <int NR, int S>
+__global__ __launch_bounds__(kBlockThreads) void ColumnNormLanesKernel(const GradArgs g,
+                                                                       const GradChunks ch) {
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int64_t cid = (int64_t)blockIdx.x * kWavesPerBlock + wave;
+  if (cid >= ch.nchunks) return;
+  const int64_t q1 = ch.begin[cid + 1];
+  double acc[S];
+#pragma unroll
+  for (int c = 0; c < S; ++c) acc[c] = 0.0;
+  for (int64_t q = ch.begin[cid] + lane; q < q1; q += kWave) {
+    const int64_t b = g.perm ? (int64_t)g.perm[q] : q;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const double* row = g.jac + g.jrow[k] + g.jstride * b;
+#pragma unroll
+      for (int c = 0; c < S; ++c) acc[c] += row[c] * row[c];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < S; ++c)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc[c] += __shfl_xor(acc[c], off, kWave);
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < S; ++c) ch.partial[cid * S + c] = acc[c];
+  }
+}
+
+// Each parameter block adds its chunks' partials in chunk order.
+template <int S>
+__global__ __launch_bounds__(kBlockThreads) void ColumnNormChunkReduceKernel(const GradArgs g,
+                                                                             const GradChunks ch) {
+  const int64_t p = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x;
+  if (p >= g.count || ch.chunk_off[p] == ch.chunk_off[p + 1]) return;
+  double acc[S];
+#pragma unroll
+  for (int c = 0; c < S; ++c) acc[c] = 0.0;
+  for (int64_t q = ch.chunk_off[p]; q < ch.chunk_off[p + 1]; ++q)
+#pragma unroll
+    for (int c = 0; c < S; ++c) acc[c] += ch.partial[q * S + c];
+  double* dst = g.grad + g.delta_base + (int64_t)S * (g.lo + p);
+#pragma unroll
+  for (int c = 0; c < S; ++c) dst[c] += acc[c];
+}
+
+// One lane per parameter block (few blocks each, not in block order).
+template <int NR, int S>
+__global__ __launch_bounds__(kBlockThreads) void ColumnNormSlotKernel(const GradArgs g) {
+  const int64_t p = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x;
+  if (p >= g.count) return;
+  double acc[S];
+#pragma unroll
+  for (int c = 0; c < S; ++c) acc[c] = 0.0;
+  for (int64_t q = g.off[p]; q < g.off[p + 1]; ++q) {
+    const int64_t b = g.perm ? (int64_t)g.perm[q] : q;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const double* row = g.jac + g.jrow[k] + g.jstride * b;
+#pragma unroll
+      for (int c = 0; c < S; ++c) acc[c] += row[c] * row[c];
+    }
+  }
+  double* dst = g.grad + g.delta_base + (int64_t)S * (g.lo + p);
+#pragma unroll
+  for (int c = 0; c < S; ++c) dst[c] += acc[c];
+}
+
 }  // namespace cse
 
 #endif  // CSE_OPERATOR_KERNELS_HPP_

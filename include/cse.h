@@ -434,6 +434,40 @@ int cse_jacobian_left_multiply(cse_evaluator* ev, const double* d_jacobian_value
 int cse_cgnr_multiply(cse_evaluator* ev, const double* d_jacobian_values, const double* d_D,
                       const double* d_x, double* d_y);
 
+/* The two column operations the trust-region loop runs on every Jacobian
+ * between Evaluate and LinearSolver::Solve, on the values in HBM: device
+ * pointers, asynchronous on the evaluator's stream, single-device evaluators
+ * with a Jacobian layout only.  Null arguments return CSE_ERR_INVALID.
+ *
+ *   cse_jacobian_squared_column_norm: d_x[c] = sum over rows of J[r][c]^2,
+ *       num_effective_parameters entries -- SparseMatrix::SquaredColumnNorm
+ *       (internal/ceres/sparse_matrix.h:81, block_sparse_matrix.cc:342,
+ *       compressed_row_sparse_matrix.cc:378), which TrustRegionMinimizer calls
+ *       for jacobi_scaling (trust_region_minimizer.cc:259-275) and
+ *       LevenbergMarquardtStrategy::ComputeStep for the LM diagonal
+ *       (levenberg_marquardt_strategy.cc:78-94).  d_x is ASSIGNED, as the
+ *       reference zeroes x first: the call zero-fills it and every group then
+ *       adds its columns' sums, so a column no cell touches reads 0 and
+ *       columns that several groups share are complete.  Deterministic on the
+ *       affine path: each parameter block sums its blocks in the fixed order of
+ *       the gradient plan (points: block order; cameras: chunks, a fixed
+ *       butterfly, an ordered chunk reduce) and the groups add in group order,
+ *       so repeats are bit-identical.  Groups on the table path (any layout,
+ *       constant blocks, tangent sizes, held cameras) and affine groups without
+ *       a gradient plan add with FP64 atomics: the split
+ *       cse_jacobian_left_multiply has.  J is read once; no scratch of
+ *       num_jacobian_values is allocated.
+ *   cse_jacobian_scale_columns: J[r][c] *= d_scale[c], in place --
+ *       SparseMatrix::ScaleColumns (sparse_matrix.h:87,
+ *       block_sparse_matrix.cc:418, compressed_row_sparse_matrix.cc:434).  One
+ *       IEEE multiply per stored value: bit-exact value * scale[column] on every
+ *       path.  Every value of every cell is touched exactly once, and nothing
+ *       else in the buffer is read or written. */
+int cse_jacobian_squared_column_norm(cse_evaluator* ev, const double* d_jacobian_values,
+                                     double* d_x);
+int cse_jacobian_scale_columns(cse_evaluator* ev, double* d_jacobian_values,
+                               const double* d_scale);
+
 /* ---- ITERATIVE_SCHUR on the device -------------------------------------
  * The implicit Schur complement of the Jacobian this evaluator wrote, for
  * the linear solve of a Schur-ordered bundle adjustment problem: replaces
