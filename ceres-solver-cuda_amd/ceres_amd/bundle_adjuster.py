@@ -98,7 +98,21 @@ def parse(argv=None):
                          "of the scaled Jacobian clamped to [1e-6, 1e32], the linear solver runs on the "
                          "scaled Jacobian and the step is un-scaled for Plus "
                          "(trust_region_minimizer.cc:259-275, 443-446)")
+    ap.add_argument("--held_cameras", type=int, default=0,
+                    help="hold cameras 0 .. N-1 constant (Problem::SetParameterBlockConstant, e.g. to fix "
+                         "the gauge): they get no columns, and the Schur solvers run on the active "
+                         "cameras' 9 (C - N) f columns.  With iterative_schur (host loop and --device_pcg, "
+                         "every preconditioner) and cgnr; the explicit Schur complements (dense_schur, "
+                         "--use_explicit_schur_complement) do not take held cameras")
     args = ap.parse_args(argv)
+    if args.held_cameras < 0:
+        raise SystemExit("--held_cameras must not be negative")
+    if args.held_cameras and args.linear_solver == "dense_schur":
+        raise SystemExit("--held_cameras needs --linear_solver iterative_schur or cgnr, not dense_schur "
+                         "(the explicit Schur complement does not take held cameras)")
+    if args.held_cameras and args.use_explicit_schur_complement:
+        raise SystemExit("--held_cameras does not go with --use_explicit_schur_complement "
+                         "(the explicit Schur complement does not take held cameras)")
     if args.use_explicit_schur_complement and args.linear_solver != "iterative_schur":
         raise SystemExit("--use_explicit_schur_complement needs --linear_solver iterative_schur, not "
                          f"{args.linear_solver}")
@@ -167,8 +181,11 @@ def solve(args, stats=None):
     manifold = args.use_quaternions and args.use_manifolds
     if args.use_quaternions and not manifold and args.linear_solver != "cgnr":
         raise SystemExit(f"{args.linear_solver} takes 9-column cameras: add --use_manifolds or use cgnr")
+    if args.held_cameras >= cams.shape[0]:
+        raise SystemExit(f"--held_cameras {args.held_cameras}: the problem has {cams.shape[0]} cameras, "
+                         "and one at least must stay free")
     prog = bal.program(cams, pts, ci[order], pi[order], obs[order], loss=loss, format=args.format,
-                       quaternion_manifold=manifold)
+                       quaternion_manifold=manifold, constant_cameras=range(args.held_cameras))
     timers.add("Preprocessor", time.perf_counter() - t0)
 
     stream = torch.cuda.current_stream(dev).cuda_stream

@@ -703,6 +703,10 @@ int cse_create(const cse_problem_desc* d, const cse_options* options, cse_evalua
   if ((rc = cse::ValidateGroups(d, &CseUserKind, &P, &ev->opts))) return bail(rc);
   ev->has_layout = P.has_layout;
   ev->groups.resize((size_t)d->num_groups);
+  // The one group's tables outlive the loop when it has held cameras: the
+  // Schur structure of such a group is planned from them.
+  cse::GroupTables held_tables;
+  bool have_held_tables = false;
   for (int gi = 0; gi < d->num_groups; ++gi) {
     Group& G = ev->groups[gi];
     const cse_residual_group& g = d->groups[gi];
@@ -710,8 +714,14 @@ int cse_create(const cse_problem_desc* d, const cse_options* options, cse_evalua
     cse::PlanGroup(d, ev->opts, gi, &P, &G, &T);
     G.user_name = P.user_names[gi];
     if ((rc = UploadGroup(g, T, &G, s))) return bail(rc);
+    if (d->num_groups == 1 && G.const0) {
+      held_tables = std::move(T);
+      have_held_tables = true;
+    }
   }
-  cse::PlanProgram(d, d->num_groups == 1 ? &ev->groups[0] : nullptr, &P);
+  cse::PlanProgram(d, d->num_groups == 1 ? &ev->groups[0] : nullptr, &P,
+                   have_held_tables ? &held_tables : nullptr);
+  held_tables = cse::GroupTables{};
   ev->res_covered = P.res_covered;
   ev->jac_covered = P.jac_covered;
   ev->bytes_res = P.bytes_res;
@@ -727,6 +737,13 @@ int cse_create(const cse_problem_desc* d, const cse_options* options, cse_evalua
   if ((rc = ev->schur.chunk_begin.upload(P.schur_chunk_begin.data(), P.schur_chunk_begin.size(), s)))
     return bail(rc);
   if ((rc = ev->schur.big.upload(P.schur_big.data(), P.schur_big.size(), s))) return bail(rc);
+  if (ev->schur.held) {
+    auto& S = ev->schur;
+    if ((rc = S.chunk_held.upload(P.schur_chunk_held.data(), P.schur_chunk_held.size(), s))) return bail(rc);
+    if ((rc = S.big_rank.upload(P.schur_big_rank.data(), P.schur_big_rank.size(), s))) return bail(rc);
+    if ((rc = S.fcell.upload(P.schur_fcell.data(), P.schur_fcell.size(), s))) return bail(rc);
+    if ((rc = S.cam_rank.upload(P.schur_cam_rank.data(), P.schur_cam_rank.size(), s))) return bail(rc);
+  }
   if ((rc = ev->cstate.upload(d->constant_state, (size_t)d->num_constant_parameters, s))) return bail(rc);
   if ((rc = ev->plus_jac.upload(d->plus_jacobians, (size_t)d->num_plus_jacobian_values, s))) return bail(rc);
   if (ev->any_general) {

@@ -187,6 +187,10 @@ struct cse_evaluator {
   // time, values and vectors bound by cse_schur_init.
   struct Schur : cse::SchurPlan {
     cse::DevBuf<int64_t> chunk_begin, big;
+    // held (cse::ProgramPlan::schur_chunk_held and the others): a block's F
+    // cell and a camera's f rows by rank.
+    cse::DevBuf<int64_t> chunk_held, big_rank;
+    cse::DevBuf<int32_t> fcell, cam_rank;
     cse::DevBuf<double> ete_inv, precond, partial, ub;
     bool ready = false;
     int preconditioner = CSE_SCHUR_IDENTITY;

@@ -235,16 +235,32 @@ cse::SchurArgs MakeSchurArgs(cse_evaluator* ev, const double* x, double* y) {
   return a;
 }
 
-template <int kMode, bool kGrad = false>
-void LaunchSchurPass(const cse::SchurArgs& a, hipStream_t s) {
+// The kHeld kernels' tables; all null without held cameras.
+cse::SchurHeldArgs MakeSchurHeldArgs(cse_evaluator* ev) {
+  const auto& S = ev->schur;
+  cse::SchurHeldArgs h{};
+  if (S.held) {
+    h.chunk_held = S.chunk_held.p;
+    h.big_rank = S.big_rank.p;
+    h.cam_rank = S.cam_rank.p;
+    h.cam_lo = ev->groups[0].grad[0].lo;
+  }
+  return h;
+}
+
+// held (multiply and back substitution of a group with held cameras): the
+// kHeld kernels; the init's point-order pass reads no F cell and is the same
+// kernel either way.
+template <int kMode, bool kGrad = false, bool kHeld = false>
+void LaunchSchurPass(const cse::SchurArgs& a, hipStream_t s, const cse::SchurHeldArgs& h = {}) {
   constexpr int W = kOperatorWavesPerWg;
   if (a.nchunks > 0)
-    hipLaunchKernelGGL((cse::SchurChunkKernel<9, kMode, W, kGrad>), dim3((unsigned)((a.nchunks + W - 1) / W)),
-                       dim3(W * cse::kWave), 0, s, a);
+    hipLaunchKernelGGL((cse::SchurChunkKernel<9, kMode, W, kGrad, kHeld>),
+                       dim3((unsigned)((a.nchunks + W - 1) / W)), dim3(W * cse::kWave), 0, s, a, h);
   if (a.nbig > 0)
-    hipLaunchKernelGGL((cse::SchurBigKernel<9, kMode, kGrad>),
+    hipLaunchKernelGGL((cse::SchurBigKernel<9, kMode, kGrad, kHeld>),
                        dim3((unsigned)((a.nbig + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
-                       dim3(cse::kBlockThreads), 0, s, a);
+                       dim3(cse::kBlockThreads), 0, s, a, h);
 }
 
 // y (f vector) += the per-f-block sums of the contributions just written.
@@ -256,6 +272,12 @@ int SchurFTail(cse_evaluator* ev, double* y, hipStream_t s) {
   ga.lo = P.lo;
   ga.grad = y;
   ga.delta_base = ev->schur.f_col_base;
+  if (ev->schur.held) {
+    // The rows through the group's delta-offset table (an active camera's is
+    // e_cols + 9 rank; a held camera has no chunk and its entry is not read).
+    ga.grad = y - ev->schur.e_cols;
+    ga.delta_tab = G.delta0.p + (P.lo - G.slot0_lo);
+  }
   return LaunchContribReduce(P, G.gcontrib.p, ga, s);
 }
 
@@ -270,19 +292,30 @@ struct SchurCameraLaunch {
   int* status;
   double* rhs;   // rhs row of the plan's first camera
   double* grad;  // gradient row of the plan's first camera (null: no gradient)
+  // held cameras (null otherwise): the F cell of each perm entry, each camera's active rank
+  const int32_t* fcell;
+  const int32_t* cam_rank;
 };
+
+template <int kDiag, bool kGrad, bool kHeld>
+void LaunchSchurCameraPassAs(const SchurCameraLaunch& L, hipStream_t s) {
+  const Group::GradPlan& P = *L.P;
+  if (P.nchunks > 0)
+    hipLaunchKernelGGL((cse::SchurCameraPassKernel<9, kDiag, kGrad, kHeld>),
+                       dim3((unsigned)((P.nchunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
+                       dim3(cse::kBlockThreads), 0, s, L.a, P.perm.p, L.ch, P.chunk_order.p, L.fcell);
+  if (P.count > 0)
+    hipLaunchKernelGGL((cse::SchurCameraFinishKernel<9, kDiag, kGrad, kHeld>),
+                       dim3((unsigned)((P.count + 63) / 64)), dim3(64), 0, s, L.ch, P.count, L.D,
+                       L.d_off, L.precond, L.status, L.rhs, L.grad, L.cam_rank);
+}
 
 template <int kDiag, bool kGrad>
 void LaunchSchurCameraPass(const SchurCameraLaunch& L, hipStream_t s) {
-  const Group::GradPlan& P = *L.P;
-  if (P.nchunks > 0)
-    hipLaunchKernelGGL((cse::SchurCameraPassKernel<9, kDiag, kGrad>),
-                       dim3((unsigned)((P.nchunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
-                       dim3(cse::kBlockThreads), 0, s, L.a, P.perm.p, L.ch, P.chunk_order.p);
-  if (P.count > 0)
-    hipLaunchKernelGGL((cse::SchurCameraFinishKernel<9, kDiag, kGrad>),
-                       dim3((unsigned)((P.count + 63) / 64)), dim3(64), 0, s, L.ch, P.count, L.D,
-                       L.d_off, L.precond, L.status, L.rhs, L.grad);
+  if (L.cam_rank)  // held cameras
+    LaunchSchurCameraPassAs<kDiag, kGrad, true>(L, s);
+  else
+    LaunchSchurCameraPassAs<kDiag, kGrad, false>(L, s);
 }
 
 int SchurCheck(cse_evaluator* ev, bool need_ready) {
@@ -295,6 +328,17 @@ int SchurCheck(cse_evaluator* ev, bool need_ready) {
                 "with its points (slot 1) as the leading e columns and its cameras after them");
   if (need_ready && !ev->schur.ready) return Fail(CSE_ERR_INVALID, "cse_schur_init has not run");
   CSE_HIP(hipSetDevice(ev->device));
+  return CSE_OK;
+}
+
+// The explicit complements: their pair plan addresses F cells by block index.
+int SchurExplicitCheck(cse_evaluator* ev, bool need_ready, const char* what) {
+  const int rc = SchurCheck(ev, need_ready);
+  if (rc) return rc;
+  if (ev->schur.held)
+    return Fail(CSE_ERR_UNSUPPORTED,
+                std::string(what) + ": the explicit Schur complement is not available with held cameras "
+                                    "(constant slot-0 blocks); the implicit operator is");
   return CSE_OK;
 }
 
@@ -340,14 +384,18 @@ int SchurInit(cse_evaluator* ev, const double* d_jacobian_values, const double* 
   const int diag = preconditioner == CSE_SCHUR_IDENTITY ? 0 : preconditioner == CSE_SCHUR_JACOBI ? 1 : 2;
   const int parts = (diag ? cse::SymCount<9>() : 0) + 9 * (grad ? 2 : 1);
   if ((rc = S.partial.ensure((size_t)std::max<int64_t>(1, P.nchunks) * parts))) return rc;
-  if (diag && (rc = S.precond.ensure((size_t)81 * P.count))) return rc;
+  if (diag && (rc = S.precond.ensure((size_t)81 * (S.held ? S.num_active : P.count)))) return rc;
   const cse::GradChunks ch{P.chunk_begin.p, P.chunk_off.p, S.partial.p, P.nchunks};
   // d_off: D index of camera lo + p = e_cols + f index = e_cols + f_col_base + 9 (lo + p).
-  const int64_t d_off = S.e_cols + S.f_col_base + 9LL * P.lo;
-  double* rhs_p = d_rhs + S.f_col_base + 9LL * P.lo;
-  double* grad_p = grad ? d_gradient + G.delta_base[0] + 9LL * P.lo : nullptr;
+  // Held cameras: the finish writes camera lo + p at its active rank, from
+  // the first f column.
+  const int64_t d_off = S.held ? S.e_cols : S.e_cols + S.f_col_base + 9LL * P.lo;
+  double* rhs_p = S.held ? d_rhs : d_rhs + S.f_col_base + 9LL * P.lo;
+  double* grad_p = !grad ? nullptr : S.held ? d_gradient + S.e_cols : d_gradient + G.delta_base[0] + 9LL * P.lo;
   int* status = ev->status.p + 1;
-  const SchurCameraLaunch L{a, &P, ch, d_D, d_off, S.precond.p, status, rhs_p, grad_p};
+  const SchurCameraLaunch L{a,      &P,    ch,     d_D, d_off, S.precond.p,
+                            status, rhs_p, grad_p, S.held ? S.fcell.p : nullptr,
+                            S.held ? S.cam_rank.p : nullptr};
   switch (diag * 2 + (grad ? 1 : 0)) {
     case 0: LaunchSchurCameraPass<0, false>(L, s); break;
     case 1: LaunchSchurCameraPass<0, true>(L, s); break;
@@ -705,7 +753,10 @@ int cse_schur_multiply(cse_evaluator* ev, const double* d_x, double* d_y) {
   hipLaunchKernelGGL(cse::SchurDiagKernel,
                      dim3((unsigned)((S.f_cols + cse::kBlockThreads - 1) / cse::kBlockThreads)),
                      dim3(cse::kBlockThreads), 0, s, S.D, S.e_cols, d_x, d_y, S.f_cols);
-  LaunchSchurPass<cse::kSchurMultiply>(MakeSchurArgs(ev, d_x, nullptr), s);
+  if (S.held)
+    LaunchSchurPass<cse::kSchurMultiply, false, true>(MakeSchurArgs(ev, d_x, nullptr), s, MakeSchurHeldArgs(ev));
+  else
+    LaunchSchurPass<cse::kSchurMultiply>(MakeSchurArgs(ev, d_x, nullptr), s);
   CSE_HIP(hipGetLastError());
   return SchurFTail(ev, d_y, s);
 }
@@ -724,10 +775,11 @@ int cse_schur_precondition(cse_evaluator* ev, const double* d_x, double* d_y) {
     return CSE_OK;
   }
   const Group::GradPlan& P = ev->groups[0].grad[0];
-  // The cameras' f rows start at f index f_col_base + 9 lo.
-  const int64_t off = S.f_col_base + 9LL * P.lo;
+  // The cameras' f rows start at f index f_col_base + 9 lo; with held
+  // cameras the blocks are the active cameras', from f index 0.
+  const int64_t off = S.held ? 0 : S.f_col_base + 9LL * P.lo;
   hipLaunchKernelGGL((cse::SchurPrecondApplyKernel<9>), dim3(grid), dim3(cse::kBlockThreads), 0, s,
-                     S.precond.p, d_x + off, d_y + off, 9LL * P.count);
+                     S.precond.p, d_x + off, d_y + off, S.held ? S.f_cols : 9LL * P.count);
   CSE_HIP(hipGetLastError());
   return CSE_OK;
 }
@@ -740,7 +792,10 @@ int cse_schur_back_substitute(cse_evaluator* ev, const double* d_x, double* d_y)
   hipStream_t s = ev->stream;
   // e part: (E^T E + D_e^2)^-1 E^T (b - F x); f part: x.
   CSE_HIP(hipMemsetAsync(d_y, 0, S.e_cols * sizeof(double), s));
-  LaunchSchurPass<cse::kSchurBack>(MakeSchurArgs(ev, d_x, d_y), s);
+  if (S.held)
+    LaunchSchurPass<cse::kSchurBack, false, true>(MakeSchurArgs(ev, d_x, d_y), s, MakeSchurHeldArgs(ev));
+  else
+    LaunchSchurPass<cse::kSchurBack>(MakeSchurArgs(ev, d_x, d_y), s);
   CSE_HIP(hipGetLastError());
   CSE_HIP(hipMemcpyAsync(d_y + S.e_cols, d_x, S.f_cols * sizeof(double), hipMemcpyDeviceToDevice, s));
   return CSE_OK;
@@ -748,7 +803,7 @@ int cse_schur_back_substitute(cse_evaluator* ev, const double* d_x, double* d_y)
 
 int cse_schur_complement_plan(cse_evaluator* ev, int64_t* num_blocks, int64_t* num_pairs,
                               int64_t* plan_bytes) {
-  int rc = SchurCheck(ev, false);
+  int rc = SchurExplicitCheck(ev, false, "cse_schur_complement_plan");
   if (rc) return rc;
   if ((rc = SchurPairPlanOf(ev, false))) return rc;
   const auto& Q = ev->schur.pairs;
@@ -759,7 +814,7 @@ int cse_schur_complement_plan(cse_evaluator* ev, int64_t* num_blocks, int64_t* n
 }
 
 int cse_schur_complement(cse_evaluator* ev, double* d_S, int64_t ld) {
-  int rc = SchurCheck(ev, true);
+  int rc = SchurExplicitCheck(ev, true, "cse_schur_complement");
   if (rc) return rc;
   auto& S = ev->schur;
   if (!d_S) return Fail(CSE_ERR_INVALID, "null pointer");
@@ -794,7 +849,7 @@ int cse_schur_complement(cse_evaluator* ev, double* d_S, int64_t ld) {
 
 int cse_schur_complement_sparse_structure(cse_evaluator* ev, int64_t* num_block_rows, int64_t* num_blocks,
                                           int64_t* device_bytes, int64_t* row_begin, int32_t* block_col) {
-  int rc = SchurCheck(ev, false);
+  int rc = SchurExplicitCheck(ev, false, "cse_schur_complement_sparse_structure");
   if (rc) return rc;
   if ((rc = SchurSparsePlanOf(ev, row_begin || block_col))) return rc;
   const auto& Z = ev->schur.sparse;
@@ -807,7 +862,7 @@ int cse_schur_complement_sparse_structure(cse_evaluator* ev, int64_t* num_block_
 }
 
 int cse_schur_complement_sparse(cse_evaluator* ev, double* d_values) {
-  int rc = SchurCheck(ev, true);
+  int rc = SchurExplicitCheck(ev, true, "cse_schur_complement_sparse");
   if (rc) return rc;
   if (!d_values) return Fail(CSE_ERR_INVALID, "null pointer");
   if ((rc = SchurSparsePlanOf(ev, true))) return rc;
@@ -836,7 +891,7 @@ int cse_schur_complement_sparse(cse_evaluator* ev, double* d_values) {
 }
 
 int cse_schur_explicit_multiply(cse_evaluator* ev, const double* d_values, const double* d_x, double* d_y) {
-  int rc = SchurCheck(ev, true);
+  int rc = SchurExplicitCheck(ev, true, "cse_schur_explicit_multiply");
   if (rc) return rc;
   if (!d_values || !d_x || !d_y) return Fail(CSE_ERR_INVALID, "null pointer");
   // Workgroups assign y while others still read x: the two may not overlap.
@@ -897,6 +952,10 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
   auto& S = ev->schur;
   const int64_t n = S.f_cols;
   if (d_rhs < d_x + n && d_x < d_rhs + n) return Fail(CSE_ERR_INVALID, "cse_schur_solve: d_x overlaps d_rhs");
+  if (d_S_values && S.held)
+    return Fail(CSE_ERR_UNSUPPORTED,
+                "cse_schur_solve: d_S_values (the explicit Schur complement) is not available with held "
+                "cameras (constant slot-0 blocks); pass NULL for the implicit operator");
   if (d_S_values && !S.sparse.uploaded)
     return Fail(CSE_ERR_INVALID,
                 "cse_schur_solve: d_S_values without the block-sparse structure "
@@ -918,8 +977,8 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
     // (cse_schur_precondition).
     const Group::GradPlan& P = ev->groups[0].grad[0];
     a.precond = S.precond.p;
-    a.pre_off = S.f_col_base + 9LL * P.lo;
-    a.pre_n = 9LL * P.count;
+    a.pre_off = S.held ? 0 : S.f_col_base + 9LL * P.lo;
+    a.pre_n = S.held ? S.f_cols : 9LL * P.count;
     if (a.pre_off < 0 || a.pre_off + a.pre_n > n || (size_t)(9 * a.pre_n) > S.precond.n)
       return Fail(CSE_ERR_INVALID, "cse_schur_solve: the preconditioner's blocks do not fit the f columns");
   }

@@ -730,14 +730,24 @@ void BuildTableRuns(const cse_problem_desc* d, const cse_residual_group& g, cons
 // (slot 0, cameras) the rest, as ITERATIVE_SCHUR's elimination ordering puts
 // them (iterative_schur_complement_solver.cc:66-80).  The e-block runs are cut
 // into wave chunks of whole runs; longer runs are listed as big.
-void BuildSchurPlan(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* P) {
+//
+// Held cameras (a const0 group; every other constant parameter is refused): a
+// block whose camera is held has an E cell and no F cell, the F cells of the
+// other blocks are packed in block order, and the active cameras of the id
+// range must tile [e_cols, num_effective) in id order, 9 columns each -- the
+// f vector then has 9 entries per active camera, by rank.  The plan adds the
+// tables that turn a block into its F cell and a camera id into its rank
+// (ProgramPlan::schur_chunk_held and the others); T = the group's tables, for
+// the slot-0 gradient plan's perm.
+void BuildSchurPlan(const cse_problem_desc* d, const GroupPlan* only, const GroupTables* T,
+                    ProgramPlan* P) {
   SchurPlan& S = P->schur;
   S = SchurPlan{};
   if (!only || d->num_groups != 1) return;
   const GroupPlan& G = *only;
-  if (!G.fuse_ok || G.policy != kAffinePacked || !SnavelyShaped(G.shape) || !P->has_layout ||
-      d->num_constant_parameters > 0)
-    return;
+  if (!G.fuse_ok || G.policy != kAffinePacked || !SnavelyShaped(G.shape) || !P->has_layout) return;
+  const bool held = G.const0;
+  if (held ? T == nullptr : d->num_constant_parameters > 0) return;
   const cse_residual_group& g = d->groups[0];
   const int32_t* ids = g.parameter_block_ids;
   const int64_t n = g.num_blocks;
@@ -749,11 +759,41 @@ void BuildSchurPlan(const cse_problem_desc* d, const GroupPlan* only, ProgramPla
     cmax = std::max(cmax, ids[2 * i]);
   }
   const int64_t e_lo = G.delta_base[1] + 3LL * pmin, e_hi = G.delta_base[1] + 3LL * pmax + 3;
-  const int64_t f_lo = G.delta_base[0] + 9LL * cmin, f_hi = G.delta_base[0] + 9LL * cmax + 9;
-  if (e_lo < 0 || f_lo != e_hi || f_hi != d->num_effective_parameters || e_lo != 0) return;
-  S.e_cols = e_hi;
-  S.f_cols = f_hi - f_lo;
-  S.f_col_base = G.delta_base[0] - S.e_cols;
+  std::vector<int32_t> cam_rank;
+  if (held) {
+    if (e_lo != 0) return;
+    // The chunk kernel moves F and E cells in 16-byte pieces.
+    if (G.jac_base[0][0] % 2 != 0 || G.jac_base[1][0] % 2 != 0) return;
+    // A constant block of the program outside the cameras' id range (a held
+    // point, a block no residual uses) is not this structure.
+    int64_t constant = 0;
+    for (int64_t b = 0; b < d->num_parameter_blocks; ++b)
+      if (d->parameter_blocks[b].is_constant && (b < cmin || b > cmax)) ++constant;
+    if (constant > 0) return;
+    const GradPlanInfo& I = T->grad_info[0];
+    if (!I.ready || I.lo != cmin || I.count != (int64_t)cmax - cmin + 1) return;
+    cam_rank.assign((size_t)I.count, -1);
+    int64_t rank = 0;
+    for (int64_t q = 0; q < I.count; ++q) {
+      const cse_parameter_block& pb = d->parameter_blocks[cmin + q];
+      if (pb.is_constant) continue;
+      if (pb.tangent_size != 9 || pb.delta_offset != e_hi + 9 * rank) return;
+      cam_rank[(size_t)q] = (int32_t)rank++;
+    }
+    if (rank == 0 || e_hi + 9 * rank != d->num_effective_parameters) return;
+    S.held = true;
+    S.num_active = rank;
+    S.e_cols = e_hi;
+    S.f_cols = 9 * rank;
+    S.f_col_base = 0;
+  } else {
+    const int64_t f_lo = G.delta_base[0] + 9LL * cmin, f_hi = G.delta_base[0] + 9LL * cmax + 9;
+    if (e_lo < 0 || f_lo != e_hi || f_hi != d->num_effective_parameters || e_lo != 0) return;
+    S.e_cols = e_hi;
+    S.f_cols = f_hi - f_lo;
+    S.f_col_base = G.delta_base[0] - S.e_cols;
+  }
+  auto active = [&](int64_t i) { return !held || cam_rank[(size_t)(ids[2 * i] - cmin)] >= 0; };
   // One pass over the runs of equal e block: small runs are packed into
   // chunks of at most a wave ([begin, end) pairs; chunks never straddle a
   // big run), big runs listed on their own.
@@ -765,8 +805,14 @@ void BuildSchurPlan(const cse_problem_desc* d, const GroupPlan* only, ProgramPla
   for (int64_t i = 1; i <= n; ++i) {
     if (i < n && ids[2 * i + 1] == ids[2 * (i - 1) + 1]) continue;
     const int64_t len = i - run_start;  // the run [run_start, i)
-    cams.assign(len, 0);
-    for (int64_t q = 0; q < len; ++q) cams[q] = ids[2 * (run_start + q)];
+    if (held) {  // a held camera has no f block to see twice
+      cams.clear();
+      for (int64_t q = run_start; q < i; ++q)
+        if (active(q)) cams.push_back(ids[2 * q]);
+    } else {
+      cams.assign(len, 0);
+      for (int64_t q = 0; q < len; ++q) cams[q] = ids[2 * (run_start + q)];
+    }
     std::sort(cams.begin(), cams.end());
     dup = dup || std::adjacent_find(cams.begin(), cams.end()) != cams.end();
     if (len > kWave) {
@@ -783,6 +829,40 @@ void BuildSchurPlan(const cse_problem_desc* d, const GroupPlan* only, ProgramPla
   S.duplicates = dup;
   S.nchunks = (int64_t)ranges.size() / 2;
   S.nbig = (int64_t)big.size() / 2;
+  if (held) {
+    // before[i]: the blocks with an active camera in [0, i) = block i's F cell.
+    std::vector<int32_t> before((size_t)n + 1);
+    int32_t cells = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      before[(size_t)i] = cells;
+      if (active(i)) ++cells;
+    }
+    before[(size_t)n] = cells;
+    P->schur_chunk_held.resize(ranges.size());
+    for (int64_t c = 0; c < S.nchunks; ++c) {
+      const int64_t i0 = ranges[2 * c], i1 = ranges[2 * c + 1];
+      uint64_t mask = 0;
+      for (int64_t i = i0; i < i1; ++i)
+        if (active(i)) mask |= (uint64_t)1 << (i - i0);
+      P->schur_chunk_held[2 * c] = before[(size_t)i0];
+      P->schur_chunk_held[2 * c + 1] = (int64_t)mask;
+    }
+    P->schur_big_rank.resize((size_t)S.nbig);
+    for (int64_t q = 0; q < S.nbig; ++q) P->schur_big_rank[(size_t)q] = before[(size_t)big[2 * q]];
+    const std::vector<int32_t>& perm = T->grad[0].perm;
+    const int64_t nperm = T->grad_info[0].nperm;
+    if (nperm != cells || (int64_t)perm.size() < nperm) {  // not the plan of these blocks
+      S = SchurPlan{};
+      ranges.clear();
+      big.clear();
+      P->schur_chunk_held.clear();
+      P->schur_big_rank.clear();
+      return;
+    }
+    P->schur_fcell.resize((size_t)std::max<int64_t>(nperm, 1), 0);
+    for (int64_t q = 0; q < nperm; ++q) P->schur_fcell[(size_t)q] = before[(size_t)perm[(size_t)q]];
+    P->schur_cam_rank = std::move(cam_rank);
+  }
   S.eligible = true;
 }
 
@@ -878,7 +958,8 @@ void PlanGroup(const cse_problem_desc* d, const cse_options& opts, int gi, Progr
                  k.s0 * I[0].count + 3 * I[1].count == d->num_effective_parameters;
 }
 
-void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* P) {
+void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* P,
+                 const GroupTables* only_tables) {
   // Plus runs: active blocks sorted by state offset, merged while
   // contiguous with a constant delta shift.
   std::vector<std::pair<int64_t, int64_t>> blocks;  // (state_offset, index)
@@ -903,7 +984,7 @@ void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* 
     else
       R.push_back({pb.state_offset, pb.size, shift});
   }
-  BuildSchurPlan(d, only, P);
+  BuildSchurPlan(d, only, only_tables, P);
   if (P->any_general) {
     P->pbs.resize((size_t)d->num_parameter_blocks);
     for (int64_t b = 0; b < d->num_parameter_blocks; ++b) {

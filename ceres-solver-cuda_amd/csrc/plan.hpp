@@ -210,8 +210,14 @@ struct SchurPlan {
   bool eligible = false;
   bool duplicates = false;  // an e block sees one f block twice
   int64_t e_cols = 0, f_cols = 0;
-  int64_t f_col_base = 0;  // f index of camera id = f_col_base + 9 id
+  int64_t f_col_base = 0;  // f index of camera id = f_col_base + 9 id (0 and unused when held)
   int64_t nchunks = 0, nbig = 0;
+  // Held cameras (a const0 group): f_cols = 9 num_active, an active camera's f
+  // index is 9 times its rank among the active ones (ProgramPlan::
+  // schur_cam_rank) and the F cell of a block is found by its rank among the
+  // blocks with an active camera (schur_chunk_held, schur_big_rank, schur_fcell).
+  bool held = false;
+  int64_t num_active = 0;
 };
 
 struct ProgramPlan {
@@ -233,6 +239,14 @@ struct ProgramPlan {
   std::vector<QuatPlusBlock> plus_quat;
   SchurPlan schur;
   std::vector<int64_t> schur_chunk_begin, schur_big;  // [begin, end) pairs
+  // schur.held only (empty otherwise).  Per wave chunk (rank0, mask): the
+  // F-cell rank of its first block -- the blocks with an active camera before
+  // it -- and bit l set when block begin + l has one; per big run its rank0;
+  // per entry q of the slot-0 gradient plan's perm the F-cell rank of block
+  // perm[q]; per camera id lo + p of that plan's range its rank among the
+  // active cameras, -1 if held.
+  std::vector<int64_t> schur_chunk_held, schur_big_rank;
+  std::vector<int32_t> schur_fcell, schur_cam_rank;
   std::vector<PbDev> pbs;                             // only when any_general
 };
 
@@ -253,8 +267,11 @@ int ValidateGroups(const cse_problem_desc* d, UserLookup lookup, ProgramPlan* P,
 void PlanGroup(const cse_problem_desc* d, const cse_options& opts, int gi, ProgramPlan* P,
                GroupPlan* G, GroupTables* T);
 // After every group: the Plus runs, the PbDev table and the Schur structure
-// (only = the plan of the program's one group, null when it has several).
-void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* P);
+// (only = the plan of the program's one group, null when it has several;
+// only_tables = that group's tables, needed for the Schur structure of a group
+// with held cameras alone: without them such a group is not eligible).
+void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* P,
+                 const GroupTables* only_tables = nullptr);
 
 // ---- The explicit Schur complement's pair plan (cse_schur_complement): which
 // residual-block pairs add into which 9 x 9 block of S.  Host only; built on

@@ -65,6 +65,22 @@ struct SchurArgs {
   int* status;             // set to 1 when a pivot of E^T E + D_e^2 is not positive
 };
 
+// The kHeld kernels' tables (held cameras: a block whose camera is held has no
+// F cell and F_b = 0; the other blocks' F cells are packed in block order from
+// f_base, and an active camera's f index is 9 times its rank).  A trailing
+// kernel argument of its own: the other instantiations never load it.
+struct SchurHeldArgs {
+  const int64_t* chunk_held;  // [nchunks][2]: F cell of the chunk's first active block, active-lane mask
+  const int64_t* big_rank;    // [nbig]: F cell of the run's first active block
+  const int32_t* cam_rank;    // [cam_count]: active rank of camera id cam_lo + p, -1 = held
+  int32_t cam_lo;
+};
+
+// Lanes below `lane` set in mask.
+__device__ __forceinline__ int MaskRank(uint64_t mask) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
 // A Cholesky pivot that can be factored: positive and finite.  Bit tests:
 // the kernels are compiled with -ffinite-math-only, which folds NaN checks.
 __device__ __forceinline__ bool PivotOk(double p) {
@@ -116,16 +132,49 @@ __device__ __forceinline__ void SymMul3(const double* M, const double* s, double
   w[2] = M[2] * s[0] + M[4] * s[1] + M[5] * s[2];
 }
 
-// One block's cells and z_b.
-template <int S0, int kMode>
+// One block's cells and z_b.  kHeld: the F cell is cell `fcell` and the
+// camera's x at rank `rank`; a block whose camera is held (rank < 0) has
+// F_b = 0, so z_b = 0 (multiply) or b_b (back substitution).
+template <int S0, int kMode, bool kHeld = false>
 __device__ __forceinline__ void SchurLoadBlock(const SchurArgs& a, int64_t i, int id0, double* F,
-                                               double* E, double* z) {
+                                               double* E, double* z, int64_t fcell = 0, int rank = 0) {
   const double2* ep = reinterpret_cast<const double2*>(a.jac + a.e_base + 6 * i);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const double2 v = ep[k];
     E[2 * k] = v.x;
     E[2 * k + 1] = v.y;
+  }
+  if constexpr (kHeld) {
+    static_assert(kMode != kSchurInit, "the init reads no F cell");
+#pragma unroll
+    for (int k = 0; k < 2 * S0; ++k) F[k] = 0.0;
+    z[0] = z[1] = 0.0;
+    if constexpr (kMode == kSchurBack) {
+      const double2 v = *reinterpret_cast<const double2*>(a.b + a.b_base + 2 * i);
+      z[0] = v.x;
+      z[1] = v.y;
+    }
+    if (rank >= 0) {
+      const double2* fp = reinterpret_cast<const double2*>(a.jac + a.f_base + 2 * S0 * fcell);
+#pragma unroll
+      for (int k = 0; k < S0; ++k) {
+        const double2 v = fp[k];
+        F[2 * k] = v.x;
+        F[2 * k + 1] = v.y;
+      }
+      const double* xc = a.x + (int64_t)S0 * rank;
+      double f0 = 0.0, f1 = 0.0;
+#pragma unroll
+      for (int k = 0; k < S0; ++k) {
+        const double xv = xc[k];
+        f0 += F[k] * xv;
+        f1 += F[S0 + k] * xv;
+      }
+      z[0] = kMode == kSchurMultiply ? f0 : z[0] - f0;
+      z[1] = kMode == kSchurMultiply ? f1 : z[1] - f1;
+    }
+    return;
   }
   {
     const double2* fp = reinterpret_cast<const double2*>(a.jac + a.f_base + 2 * S0 * i);
@@ -209,9 +258,17 @@ __device__ __forceinline__ void SchurStoreU(const SchurArgs& a, int64_t i, const
 // Init reads no F cell: it writes u_b per block for the camera pass.
 // kGrad (kSchurInit only): also the gradient g = J^T r = -J^T b, its e rows
 // written here (-E^T b per e block), b_b beside u_b for its f rows.
-template <int S0, int kMode, int kWPB = kWavesPerBlock, bool kGrad = false>
-__global__ __launch_bounds__(kWPB * kWave) void SchurChunkKernel(const SchurArgs a) {
+// kHeld (multiply and back substitution; the init reads no F cell and serves
+// held groups as it is): the chunk's F segment is the cells of its lanes with
+// an active camera, contiguous from cell rank0 = chunk_held[2 c]; such a lane
+// finds its cell at its rank among them (the mask, chunk_held[2 c + 1]) and its
+// x at the camera's active rank; a held lane keeps F = 0 and x_c = 0, and the
+// zeros it stores as its contribution are never read.
+template <int S0, int kMode, int kWPB = kWavesPerBlock, bool kGrad = false, bool kHeld = false>
+__global__ __launch_bounds__(kWPB * kWave) void SchurChunkKernel(const SchurArgs a,
+                                                                 const SchurHeldArgs h) {
   static_assert(!kGrad || kMode == kSchurInit, "the gradient comes with the init pass");
+  static_assert(!kHeld || kMode != kSchurInit, "the init has no held variant");
   constexpr int S0p = (S0 + 1) & ~1;
   constexpr int kRec = S0p;                 // doubles per contribution record
   constexpr int kF = 2 * S0;                // doubles per F cell
@@ -230,10 +287,26 @@ __global__ __launch_bounds__(kWPB * kWave) void SchurChunkKernel(const SchurArgs
   const int nb = (int)(a.chunk_begin[2 * c + 1] - i0);
   const bool active = lane < nb;
   const int64_t i = active ? i0 + lane : i0;
+  // kHeld: the lane's block has an F cell (no bit is set at or above nb), at
+  // cell `fl` of the image.
+  bool has_f = true;
+  int fl = lane;
+  int64_t fseg = i0;
+  int nf = nb;
+  if constexpr (kHeld) {
+    const int64_t r0 = h.chunk_held[2 * c], m = h.chunk_held[2 * c + 1];
+    const uint32_t mlo = __builtin_amdgcn_readfirstlane((uint32_t)m);
+    const uint32_t mhi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)m >> 32));
+    const uint64_t mask = ((uint64_t)mhi << 32) | mlo;
+    has_f = (mask >> lane) & 1;
+    fl = MaskRank(mask);
+    fseg = r0;
+    nf = __builtin_popcountll(mask);
+  }
   {
-    const double* segF = a.jac + a.f_base + (int64_t)kF * i0;
+    const double* segF = a.jac + a.f_base + (int64_t)kF * fseg;
     const double* segE = a.jac + a.e_base + 6LL * i0;
-    const int pf = (kF / 2) * nb, pe = 3 * nb;  // 16-byte pieces
+    const int pf = (kF / 2) * nf, pe = 3 * nb;  // 16-byte pieces
     if constexpr (kMode != kSchurInit) {
 #pragma unroll
       for (int k = 0; k < kF / 2; ++k) {
@@ -258,9 +331,16 @@ __global__ __launch_bounds__(kWPB * kWave) void SchurChunkKernel(const SchurArgs
   }
   double xc[S0];
   if constexpr (kMode != kSchurInit) {
-    const double* xp = a.x + a.f_col_base + (int64_t)S0 * id0;
+    if constexpr (kHeld) {
+      const int rank = h.cam_rank[id0 - h.cam_lo];
+      const double* xp = a.x + (int64_t)S0 * (rank < 0 ? 0 : rank);
 #pragma unroll
-    for (int k = 0; k < S0; ++k) xc[k] = xp[k];
+      for (int k = 0; k < S0; ++k) xc[k] = has_f ? xp[k] : 0.0;
+    } else {
+      const double* xp = a.x + a.f_col_base + (int64_t)S0 * id0;
+#pragma unroll
+      for (int k = 0; k < S0; ++k) xc[k] = xp[k];
+    }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
@@ -268,9 +348,9 @@ __global__ __launch_bounds__(kWPB * kWave) void SchurChunkKernel(const SchurArgs
   if constexpr (kMode != kSchurInit) {
 #pragma unroll
     for (int k = 0; k < kF / 2; ++k) {
-      const double2 v = reinterpret_cast<const double2*>(im + kF * lane)[k];
-      F[2 * k] = v.x;
-      F[2 * k + 1] = v.y;
+      const double2 v = reinterpret_cast<const double2*>(im + kF * fl)[k];
+      F[2 * k] = kHeld && !has_f ? 0.0 : v.x;
+      F[2 * k + 1] = kHeld && !has_f ? 0.0 : v.y;
     }
   }
 #pragma unroll
@@ -377,24 +457,49 @@ __global__ __launch_bounds__(kWPB * kWave) void SchurChunkKernel(const SchurArgs
 
 // One wave per e block with more rows than a wave: the rows are walked
 // twice, once for the sums and once for the contributions.
-template <int S0, int kMode, bool kGrad = false>
-__global__ __launch_bounds__(kBlockThreads) void SchurBigKernel(const SchurArgs a) {
+// kHeld (multiply and back substitution): both walks go by whole strides of
+// 64 rows and carry the F cell of the stride's first active row, from
+// big_rank[q]; a row's cell is that plus its rank among the stride's active
+// rows (a ballot), so the two walks agree on every cell.
+template <int S0, int kMode, bool kGrad = false, bool kHeld = false>
+__global__ __launch_bounds__(kBlockThreads) void SchurBigKernel(const SchurArgs a,
+                                                                const SchurHeldArgs h) {
+  static_assert(!kHeld || kMode != kSchurInit, "the init has no held variant");
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   const int64_t q = (int64_t)blockIdx.x * kWavesPerBlock + wave;
   if (q >= a.nbig) return;
   const int64_t i0 = a.big[2 * q], i1 = a.big[2 * q + 1];
   const int id1 = (int)(reinterpret_cast<const long long*>(a.ids)[i0] >> 32);
   double s[3] = {0.0, 0.0, 0.0}, A[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int64_t i = i0 + lane; i < i1; i += kWave) {
-    const int id0 = (int)reinterpret_cast<const long long*>(a.ids)[i];
-    double F[2 * S0], E[6], z[2], sb[3], Ab[6];
-    SchurLoadBlock<S0, kMode>(a, i, id0, F, E, z);
-    SchurEProducts(E, z, sb, Ab);
+  if constexpr (kHeld) {
+    int64_t cell = h.big_rank[q];
+    for (int64_t ib = i0; ib < i1; ib += kWave) {
+      const int64_t i = ib + lane;
+      const bool in = i < i1;
+      const int id0 = (int)reinterpret_cast<const long long*>(a.ids)[in ? i : i0];
+      const int rank = in ? h.cam_rank[id0 - h.cam_lo] : -1;
+      const uint64_t act = __ballot(rank >= 0);
+      if (in) {
+        double F[2 * S0], E[6], z[2], sb[3], Ab[6];
+        SchurLoadBlock<S0, kMode, true>(a, i, id0, F, E, z, cell + MaskRank(act), rank);
+        SchurEProducts(E, z, sb, Ab);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] += sb[k];
-    if constexpr (kMode == kSchurInit) {
+        for (int k = 0; k < 3; ++k) s[k] += sb[k];
+      }
+      cell += __builtin_popcountll(act);
+    }
+  } else {
+    for (int64_t i = i0 + lane; i < i1; i += kWave) {
+      const int id0 = (int)reinterpret_cast<const long long*>(a.ids)[i];
+      double F[2 * S0], E[6], z[2], sb[3], Ab[6];
+      SchurLoadBlock<S0, kMode>(a, i, id0, F, E, z);
+      SchurEProducts(E, z, sb, Ab);
 #pragma unroll
-      for (int k = 0; k < 6; ++k) A[k] += Ab[k];
+      for (int k = 0; k < 3; ++k) s[k] += sb[k];
+      if constexpr (kMode == kSchurInit) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) A[k] += Ab[k];
+      }
     }
   }
 #pragma unroll
@@ -447,6 +552,21 @@ __global__ __launch_bounds__(kBlockThreads) void SchurBigKernel(const SchurArgs 
       const double2 v = *reinterpret_cast<const double2*>(a.b + a.b_base + 2 * i);
       const double z[2] = {v.x, v.y};
       SchurStoreU<kGrad>(a, i, E, z, w);
+    }
+  } else if constexpr (kHeld) {
+    int64_t cell = h.big_rank[q];
+    for (int64_t ib = i0; ib < i1; ib += kWave) {
+      const int64_t i = ib + lane;
+      const bool in = i < i1;
+      const int id0 = (int)reinterpret_cast<const long long*>(a.ids)[in ? i : i0];
+      const int rank = in ? h.cam_rank[id0 - h.cam_lo] : -1;
+      const uint64_t act = __ballot(rank >= 0);
+      if (in) {
+        double F[2 * S0], E[6], z[2];
+        SchurLoadBlock<S0, kMode, true>(a, i, id0, F, E, z, cell + MaskRank(act), rank);
+        SchurContrib<S0>(a, i, F, E, z, w);  // zeros for a held row, never read
+      }
+      cell += __builtin_popcountll(act);
     }
   } else {
     for (int64_t i = i0 + lane; i < i1; i += kWave) {
@@ -519,11 +639,14 @@ constexpr int SymCount() { return S0 * (S0 + 1) / 2; }
 template <int S0, int kDiag, bool kGrad>
 constexpr int SchurPartCount() { return (kDiag ? SymCount<S0>() : 0) + S0 + (kGrad ? S0 : 0); }
 
-template <int S0, int kDiag, bool kGrad>
+// kHeld: block perm[q]'s F cell is cell fcell[q] (held cameras have no entry
+// in perm); everything else is by block index, as without held cameras.
+template <int S0, int kDiag, bool kGrad, bool kHeld = false>
 __global__ __launch_bounds__(kBlockThreads) void SchurCameraPassKernel(const SchurArgs a,
                                                                        const int32_t* perm,
                                                                        const GradChunks ch,
-                                                                       const int32_t* order) {
+                                                                       const int32_t* order,
+                                                                       const int32_t* fcell) {
   static_assert(S0 + 2 <= 16, "A^T B in one 16 x 16 f64 tile");
   constexpr int T = kDiag ? SymCount<S0>() : 0;
   constexpr int kPart = SchurPartCount<S0, kDiag, kGrad>();
@@ -550,7 +673,8 @@ __global__ __launch_bounds__(kBlockThreads) void SchurCameraPassKernel(const Sch
     if (bl < nb) {
       i = perm[qs + bl];
       // half 0: F doubles [0, 2 kP0); half 1: [2 kP0, 2 S0), u_b (and b_b).
-      const double2* fp = reinterpret_cast<const double2*>(a.jac + a.f_base + 2 * S0 * i);
+      const int64_t fi = kHeld ? (int64_t)fcell[qs + bl] : i;
+      const double2* fp = reinterpret_cast<const double2*>(a.jac + a.f_base + 2 * S0 * fi);
       double* r0 = slab + (2 * bl) * kW;
       if (h == 0) {
 #pragma unroll
@@ -653,15 +777,23 @@ __global__ __launch_bounds__(kBlockThreads) void SchurCameraPassKernel(const Sch
 // factor (llt().solve(Identity), as the reference's
 // BlockRandomAccessDiagonalMatrix::Invert and AddDiagonalAndInvert) stored
 // as a full S0 x S0 matrix.
-template <int S0, int kDiag, bool kGrad>
+// kHeld: camera p of the plan's range writes at its active rank cam_rank[p]
+// (rhs, grad, D and P then start at the first active camera's); a held one
+// (rank -1) writes nothing and raises no status.
+template <int S0, int kDiag, bool kGrad, bool kHeld = false>
 __global__ __launch_bounds__(64) void SchurCameraFinishKernel(const GradChunks ch, int64_t count,
                                                               const double* D, int64_t d_off,
                                                               double* P, int* status, double* rhs,
-                                                              double* grad) {
+                                                              double* grad, const int32_t* cam_rank) {
   constexpr int T = kDiag ? SymCount<S0>() : 0;
   constexpr int kPart = SchurPartCount<S0, kDiag, kGrad>();
   const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (p >= count) return;
+  int64_t o = p;  // the camera's place in the outputs
+  if constexpr (kHeld) {
+    o = cam_rank[p];
+    if (o < 0) return;
+  }
   {
     double ru[S0], rb[S0];
 #pragma unroll
@@ -676,10 +808,10 @@ __global__ __launch_bounds__(64) void SchurCameraFinishKernel(const GradChunks c
       }
     }
 #pragma unroll
-    for (int k = 0; k < S0; ++k) rhs[(int64_t)S0 * p + k] = ru[k];
+    for (int k = 0; k < S0; ++k) rhs[(int64_t)S0 * o + k] = ru[k];
     if constexpr (kGrad) {
 #pragma unroll
-      for (int k = 0; k < S0; ++k) grad[(int64_t)S0 * p + k] = -rb[k];
+      for (int k = 0; k < S0; ++k) grad[(int64_t)S0 * o + k] = -rb[k];
     }
   }
   if constexpr (kDiag != 0) {
@@ -700,7 +832,7 @@ __global__ __launch_bounds__(64) void SchurCameraFinishKernel(const GradChunks c
     if (D) {
 #pragma unroll
       for (int r = 0; r < S0; ++r) {
-        const double d = D[d_off + (int64_t)S0 * p + r];
+        const double d = D[d_off + (int64_t)S0 * o + r];
         L[r][r] += d * d;
       }
     }
@@ -725,7 +857,7 @@ __global__ __launch_bounds__(64) void SchurCameraFinishKernel(const GradChunks c
         L[r][j] = v * inv;
       }
     }
-    double* out = P + (int64_t)S0 * S0 * p;
+    double* out = P + (int64_t)S0 * S0 * o;
     if (!ok) {
       *status = 1;
       for (int k = 0; k < S0 * S0; ++k) out[k] = 0.0;

@@ -484,7 +484,15 @@ int cse_jacobian_scale_columns(cse_evaluator* ev, double* d_jacobian_values,
  * library's Snavely kinds or a user kind; the operators read only the
  * Jacobian) on the affine BlockSparseMatrix path whose points occupy the effective columns
  * [0, num_cols_e) and cameras the rest, as ITERATIVE_SCHUR's elimination
- * ordering gives.  All device pointers, asynchronous on the evaluator's
+ * ordering gives.  Held cameras (constant slot-0 blocks,
+ * Problem::SetParameterBlockConstant) are allowed when the active cameras'
+ * columns tile [num_cols_e, num_effective_parameters) in id order, 9 each: a
+ * held camera has no row or column anywhere, num_cols_f = 9 x (active
+ * cameras), and a block with a held camera enters only the point sums
+ * (F_b = 0).  Any other constant parameter block (a held point) is refused,
+ * and on a program with held cameras so are the explicit complements below
+ * (cse_schur_complement*, cse_schur_explicit_multiply, cse_schur_solve with
+ * d_S_values).  All device pointers, asynchronous on the evaluator's
  * stream, deterministic. */
 enum cse_schur_preconditioner {
   CSE_SCHUR_IDENTITY = 0,     /* IDENTITY: M^-1 = I */
