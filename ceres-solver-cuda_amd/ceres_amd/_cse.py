@@ -61,6 +61,10 @@ SCHUR_IDENTITY = 0
 SCHUR_JACOBI = 1
 SCHUR_SCHUR_JACOBI = 2
 
+# cse_cgnr_preconditioner
+CGNR_IDENTITY = 0
+CGNR_JACOBI = 1
+
 # cse_cg_termination (= LinearSolverTerminationType) and cse_cg_reason
 CG_SUCCESS = 0
 CG_NO_CONVERGENCE = 1
@@ -203,6 +207,10 @@ SIGNATURES = {
     "cse_cg_default_options": (None, [C.POINTER(cse_cg_options)]),
     "cse_schur_solve": (C.c_int, [C.c_void_p, C.POINTER(cse_cg_options), C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.POINTER(cse_cg_summary)]),
+    "cse_cgnr_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "cse_cgnr_precondition": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cse_cgnr_solve": (C.c_int, [C.c_void_p, C.POINTER(cse_cg_options), C.c_void_p, C.c_void_p,
+                                 C.POINTER(cse_cg_summary)]),
     "cse_create_multi": (C.c_int, [C.POINTER(cse_problem_desc), C.POINTER(cse_options),
                                    P_i32, C.c_int32, C.POINTER(C.c_void_p)]),
     "cse_shard_info": (C.c_int, [C.c_void_p, P_i32, P_i64, P_i32]),

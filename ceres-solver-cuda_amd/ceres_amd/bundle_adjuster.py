@@ -90,6 +90,18 @@ def parse(argv=None):
                          "measured at 49 cameras; 16 already loses to the trailing iterations), 1 "
                          "from about a thousand cameras on, where a product is long against a host "
                          "wait; DESIGN 3.6c")
+    ap.add_argument("--device_cgnr", action="store_true",
+                    help="cgnr only: CudaCgnrSolver on the device (cgnr_solver.cc:218-387) instead of the "
+                         "torch loop on the host: per solve cse_cgnr_init(J, sqrt(lambda D), -r) -- the "
+                         "right-hand side J^T b and the preconditioner -- and cse_cgnr_solve with "
+                         "r_tolerance = eta, q_tolerance = 0 and no residual reset, from the zero start")
+    ap.add_argument("--cgnr_preconditioner", default="jacobi", choices=["jacobi", "identity"],
+                    help="--device_cgnr: jacobi is the reference's BlockCRSJacobiPreconditioner, per "
+                         "parameter block (sum J^T J + D^2)^-1 (the host loop's is the scalar "
+                         "1 / ((1 + lambda) diag J^T J))")
+    ap.add_argument("--cgnr_check_period", type=int, default=1,
+                    help="--device_cgnr: the host looks at the device state after this many enqueued "
+                         "iterations (as --pcg_check_period)")
     ap.add_argument("--jacobi_scaling", action="store_true",
                     help="Solver::Options::jacobi_scaling (on by default in the reference, off here so "
                          "that earlier runs keep their iterates): at iteration 0 scaling = 1 / (1 + "
@@ -122,6 +134,10 @@ def parse(argv=None):
         raise SystemExit("--pcg_termination quadratic needs --device_pcg")
     if args.pcg_check_period < 1:
         raise SystemExit("--pcg_check_period must be at least 1")
+    if args.device_cgnr and args.linear_solver != "cgnr":
+        raise SystemExit(f"--device_cgnr needs --linear_solver cgnr, not {args.linear_solver}")
+    if args.cgnr_check_period < 1:
+        raise SystemExit("--cgnr_check_period must be at least 1")
     return args
 
 
@@ -253,6 +269,36 @@ def solve(args, stats=None):
             p = z + (rz_new / rz) * p
             rz = rz_new
         return dx, it
+
+    if args.device_cgnr:
+        cgnr_pre = {"identity": ca._cse.CGNR_IDENTITY, "jacobi": ca._cse.CGNR_JACOBI}[args.cgnr_preconditioner]
+        cgnr_rhs = torch.empty(n, dtype=f64, device=dev)
+        cgnr_neg_r = torch.empty(m, dtype=f64, device=dev)
+        cgnr_options = ca._cse.cg_options(r_tolerance=args.eta, q_tolerance=0.0,
+                                          residual_reset_period=args.max_linear_solver_iterations + 1,
+                                          max_num_iterations=args.max_linear_solver_iterations,
+                                          check_period=args.cgnr_check_period,
+                                          flags=ca._cse.CG_ZERO_INITIAL_GUESS)
+
+    def cgnr_device(lam):
+        # CudaCgnrSolver::SolveImpl (cgnr_solver.cc:350-387): Atb = J^T b and the
+        # preconditioner (cse_cgnr_init), then ConjugateGradientsSolver from
+        # x = 0 (cse_cgnr_solve), all on the device.
+        torch.neg(r, out=cgnr_neg_r)
+        sqrt_lam_d = torch.sqrt(lam * D)
+        ev.cgnr_init_device(jac.data_ptr(), sqrt_lam_d.data_ptr(), cgnr_neg_r.data_ptr(),
+                            cgnr_rhs.data_ptr(), cgnr_pre)
+        dx = torch.empty(n, dtype=f64, device=dev)
+        summary = ev.cgnr_solve_device(cgnr_rhs.data_ptr(), dx.data_ptr(), cgnr_options)
+        if summary.termination_type == ca._cse.CG_FAILURE:
+            raise SystemExit(f"device CGNR failed (reason {summary.reason})")
+        # A block the JACOBI init could not factor was left zero and raised the
+        # status word (that init clears it first); the next evaluation would
+        # overwrite it unread.
+        if cgnr_pre == ca._cse.CGNR_JACOBI and ev.wait() != 0:
+            raise SystemExit("device CGNR: a block of J^T J + lambda D is not positive definite "
+                             "(cse_cgnr_init raised the status word)")
+        return dx, summary.num_iterations
 
     if args.linear_solver != "cgnr":
         e_cols, f_cols = ev.schur_structure()
@@ -419,7 +465,7 @@ def solve(args, stats=None):
             D.clamp_(min=1e-6)
             d_stale = False
         solver = {"iterative_schur": schur_solve, "dense_schur": dense_schur_solve,
-                  "cgnr": cgnr}[args.linear_solver]
+                  "cgnr": cgnr_device if args.device_cgnr else cgnr}[args.linear_solver]
         dx, cg_iters = timed("Linear solver", lambda: solver(1.0 / radius))
         # dx is the step of the (scaled) linear system; Plus takes delta =
         # step .* scaling (trust_region_minimizer.cc:443-446).

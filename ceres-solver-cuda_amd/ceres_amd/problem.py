@@ -677,6 +677,32 @@ class Evaluator:
         return _cse.check(_cse.lib().cse_cgnr_multiply(self.handle, d_jacobian, d_D, d_x, d_y),
                           "cse_cgnr_multiply")
 
+    def cgnr_init_device(self, d_jacobian, d_D, d_b=None, d_rhs=None, preconditioner=_cse.CGNR_JACOBI):
+        """Binds J and D (may be None) for cgnr_precondition_device and
+        cgnr_solve_device, writes rhs = J^T b when d_b and d_rhs are given
+        (both or neither) and, for CGNR_JACOBI, builds the reference's
+        BlockCRSJacobiPreconditioner on the device: per parameter block
+        (sum J^T J + D^2)^-1 (cse_cgnr_init).  J and D must stay valid until the
+        next init."""
+        return _cse.check(_cse.lib().cse_cgnr_init(self.handle, d_jacobian, d_D, d_b, d_rhs,
+                                                   int(preconditioner)), "cse_cgnr_init")
+
+    def cgnr_precondition_device(self, d_x, d_y):
+        """y += M^-1 x for the preconditioner chosen at cgnr_init_device
+        (CGNR_IDENTITY: y += x); num_effective_parameters entries."""
+        return _cse.check(_cse.lib().cse_cgnr_precondition(self.handle, d_x, d_y),
+                          "cse_cgnr_precondition")
+
+    def cgnr_solve_device(self, d_rhs, d_x, options):
+        """(J^T J + D^2) x = rhs by the reference's preconditioned conjugate
+        gradients, all on the device (cse_cgnr_solve, CudaCgnrSolver): options
+        is a _cse.cse_cg_options; d_x holds the initial guess and receives the
+        solution.  Returns the _cse.cse_cg_summary."""
+        summary = _cse.cse_cg_summary()
+        _cse.check(_cse.lib().cse_cgnr_solve(self.handle, C.byref(options), d_rhs, d_x,
+                                             C.byref(summary)), "cse_cgnr_solve")
+        return summary
+
     def squared_column_norm_device(self, d_jacobian, d_out):
         """out[c] = sum over rows of J[r][c]^2 on the device, num_effective_parameters
         entries, assigned (SparseMatrix::SquaredColumnNorm); bit-identical repeats on

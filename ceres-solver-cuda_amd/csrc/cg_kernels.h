@@ -1,5 +1,6 @@
 // cg_kernels.h -- the launchers of cse_schur_solve's vector kernels
-// (cg_kernels.hpp), a translation unit of their own (cg_kernels.hip): it is
+// (cg_kernels.hpp) and of cse_cgnr_solve's (cg_sliced_kernels.hpp), a
+// translation unit of their own (cg_kernels.hip): it is
 // built without -ffinite-math-only, which the evaluation kernels' unit needs
 // and under which ConjugateGradientsSolver's tests for infinite scalars
 // (conjugate_gradients_solver.h:116-118, :196, :208) would be folded away.
@@ -11,6 +12,7 @@
 #include <cstdint>
 
 #include "cg_state.hpp"
+#include "host_shared.hpp"
 
 namespace cse {
 
@@ -37,6 +39,41 @@ void LaunchCgInit(const CgArgs& a, bool zero_guess, hipStream_t s);
 void LaunchCgInitialResidual(const CgArgs& a, hipStream_t s);
 void LaunchCgDirection(const CgArgs& a, hipStream_t s);
 void LaunchCgUpdate(CgUpdateMode mode, const CgArgs& a, hipStream_t s);
+
+// ---- cse_cgnr_solve's vector kernels (cg_sliced_kernels.hpp): any length, one
+// workgroup of kCgSliceThreads lanes per slice of kCgSliceEntries entries.
+constexpr int kCgSliceEntries = 2048;
+constexpr int kCgSliceWaves = 4;
+constexpr int kCgSliceThreads = kCgSliceWaves * 64;
+
+inline int64_t CgSliceCount(int64_t n) { return n > 0 ? (n + kCgSliceEntries - 1) / kCgSliceEntries : 1; }
+
+struct CgSlicedArgs {
+  int64_t n;          // num_effective_parameters
+  const double* rhs;
+  double* x;
+  double *p, *r, *z, *tmp;  // the reference's four scratch vectors (q is z)
+  const double* zr;   // what the direction kernels read as z: z = M^-1 r, or r under IDENTITY
+  CgState* state;
+  CgParams params;
+  double* partial;    // [2][CgSliceCount(n)]: the slices' partial sums
+  int* counter;       // the hand-over counter, 0 between launches
+  // The block-Jacobi preconditioner (null tab: IDENTITY).
+  const CgnrBlock* tab;
+  int64_t ntab;
+  const double* precond;
+};
+
+void LaunchCgSlicedInit(const CgSlicedArgs& a, bool zero_guess, hipStream_t s);
+void LaunchCgSlicedInitialResidual(const CgSlicedArgs& a, hipStream_t s);
+// z = M^-1 r (JACOBI), rho and its tests, then p.
+void LaunchCgSlicedDirection(const CgSlicedArgs& a, hipStream_t s);
+// Full and X: p'q and its tests first.
+void LaunchCgSlicedUpdate(CgUpdateMode mode, const CgSlicedArgs& a, hipStream_t s);
+// y = M x (assign) or y += M x, one parameter block per lane; state: null, or
+// the solve's (nothing is written once it is done).
+void LaunchCgnrApplyBlocks(const CgnrBlock* tab, int64_t ntab, const double* values, const double* x,
+                           double* y, bool assign, const CgState* state, hipStream_t s);
 
 }  // namespace cse
 

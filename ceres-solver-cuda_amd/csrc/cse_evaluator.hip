@@ -732,6 +732,9 @@ int cse_create(const cse_problem_desc* d, const cse_options* options, cse_evalua
   ev->plus_runs_host = std::move(P.plus_runs);
   ev->plus_quat_host = std::move(P.plus_quat);
   static_cast<cse::SchurPlan&>(ev->schur) = P.schur;
+  // cse_cgnr_init's block table, as runs (a pass over the parameter blocks and
+  // a few bytes; the first JACOBI init expands and uploads it).
+  if (ev->has_layout) cse::PlanCgnrBlocks(d, &ev->cgnr.plan);
 
   // Program-level device state.
   if ((rc = ev->schur.chunk_begin.upload(P.schur_chunk_begin.data(), P.schur_chunk_begin.size(), s)))

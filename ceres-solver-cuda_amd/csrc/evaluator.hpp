@@ -224,6 +224,28 @@ struct cse_evaluator {
     cse::DevBuf<cse::CgState> state;
     cse::CgState* state_host = nullptr;  // pinned
   } cg;
+  // CGNR on the device (cse_cgnr_init, cse_cgnr_precondition, cse_cgnr_solve).
+  // `plan` is the block table as cse_create planned it from the descriptor, in
+  // runs; the first JACOBI init expands it, uploads it and looks each affine
+  // slot's first block up (value_base).  The solve shares cg.state with
+  // cse_schur_solve and has vectors of its own (num_effective_parameters each).
+  struct Cgnr {
+    cse::CgnrBlockPlan plan;
+    bool uploaded = false;
+    int64_t ntab = 0;
+    cse::DevBuf<cse::CgnrBlock> blocks;
+    // Per group, per slot: the value offset of parameter block `lo` of the
+    // slot's gradient plan when the plan's blocks are consecutive table entries
+    // of the slot's size; -1 otherwise (that group takes GramBlockKernel).
+    std::vector<int64_t> value_base;
+    cse::DevBuf<double> values;         // the inverse blocks
+    cse::DevBuf<double> chunk_partial;  // the Gram's chunk partials (largest wave plan)
+    cse::DevBuf<double> vectors, partial;
+    cse::DevBuf<int> counter;
+    bool ready = false;
+    int preconditioner = CSE_CGNR_IDENTITY;
+    const double *jac = nullptr, *D = nullptr;
+  } cgnr;
 };
 
 namespace cse {

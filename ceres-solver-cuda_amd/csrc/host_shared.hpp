@@ -63,6 +63,20 @@ struct QuatPlusBlock {
   int32_t pad;
 };
 
+// One non-constant parameter block of cse_cgnr_init's block-Jacobi
+// preconditioner (PlanCgnrBlocks in plan.cpp): its tangent_size x tangent_size
+// row-major block starts at value_offset of the packed values, as
+// BlockCRSJacobiPreconditioner stores its blocks.
+struct CgnrBlock {
+  int64_t delta_offset;
+  int64_t value_offset;
+  int32_t tangent_size;
+  int32_t pad;
+};
+
+// Largest block JACOBI takes (the affine path's slot limit).
+constexpr int kCgnrMaxBlockColumns = 16;
+
 // Flags of a table group's per-chunk store run record (BuildTableRuns in
 // plan.cpp writes them, TableStores in evaluate_kernel.hpp reads them).
 constexpr int kTableRunFlagResiduals = 1, kTableRunFlagBsm = 2, kTableRunFlagCrs = 4;

@@ -2,14 +2,16 @@
 // solver makes on the evaluator (evaluator.hpp): J x, J^T x and CGNR
 // (operator_kernels.hpp), the column norms and ScaleColumns
 // (column_kernels.hpp), the implicit Schur complement (schur_kernels.hpp),
-// the explicit one (schur_complement_kernels.hpp) and cse_schur_solve
-// (cg_kernels.h).  The gradient post-pass kernels are launched through
-// evaluator.hpp's functions: they stay instantiated in cse_evaluator.hip.
+// the explicit one (schur_complement_kernels.hpp), cse_schur_solve and CGNR on
+// the device (cgnr_kernels.hpp; the vector kernels through cg_kernels.h).  The
+// gradient post-pass kernels are launched through evaluator.hpp's functions:
+// they stay instantiated in cse_evaluator.hip.
 #include <algorithm>
 #include <cstring>
 #include <new>
 
 #include "cg_kernels.h"
+#include "cgnr_kernels.hpp"
 #include "column_kernels.hpp"
 #include "evaluator.hpp"
 #include "kernel_pickers.hpp"
@@ -552,15 +554,34 @@ cse::SchurPairArgs MakeSchurPairArgs(cse_evaluator* ev) {
 // cse_schur_solve: the reference's conjugate gradients on the device
 // (cg_state.hpp, cg_kernels.hpp)
 // ---------------------------------------------------------------------------
-// The loop of conjugate_gradients_solver.h:108-305 over any operator: `op(x, y)`
-// enqueues y = A x on the stream `s` and returns a cse status; the
-// preconditioner is the one described in `a` (applied inside
-// CgDirectionKernel).  The host enqueues check_period iterations, copies the
-// state to pinned memory, waits once and stops or goes on; it computes no
+// The loop of conjugate_gradients_solver.h:108-305 over any operator and either
+// set of vector kernels: `op(x, y)` enqueues y = A x on the stream `s` and
+// returns a cse status; `L` launches the vector kernels over its arguments
+// L.a (SchurCgLaunch: cg_kernels.hpp's one-workgroup kernels, the
+// preconditioner applied inside CgDirectionKernel; CgnrCgLaunch:
+// cg_sliced_kernels.hpp's).  The host enqueues check_period iterations, copies
+// the state to pinned memory, waits once and stops or goes on; it computes no
 // scalar of the iteration.  Nothing is allocated here.
-template <class Op>
-int CgSolve(const cse::CgArgs& a, const cse_cg_options& o, cse::CgState* state_host, hipStream_t s,
-            Op&& op, cse_cg_summary* summary) {
+struct SchurCgLaunch {
+  cse::CgArgs a;
+  void Init(bool zero_guess, hipStream_t s) const { cse::LaunchCgInit(a, zero_guess, s); }
+  void InitialResidual(hipStream_t s) const { cse::LaunchCgInitialResidual(a, s); }
+  void Direction(hipStream_t s) const { cse::LaunchCgDirection(a, s); }
+  void Update(cse::CgUpdateMode mode, hipStream_t s) const { cse::LaunchCgUpdate(mode, a, s); }
+};
+
+struct CgnrCgLaunch {
+  cse::CgSlicedArgs a;
+  void Init(bool zero_guess, hipStream_t s) const { cse::LaunchCgSlicedInit(a, zero_guess, s); }
+  void InitialResidual(hipStream_t s) const { cse::LaunchCgSlicedInitialResidual(a, s); }
+  void Direction(hipStream_t s) const { cse::LaunchCgSlicedDirection(a, s); }
+  void Update(cse::CgUpdateMode mode, hipStream_t s) const { cse::LaunchCgSlicedUpdate(mode, a, s); }
+};
+
+template <class Launch, class Op>
+int CgSolve(const char* what, const Launch& L, const cse_cg_options& o, cse::CgState* state_host,
+            hipStream_t s, Op&& op, cse_cg_summary* summary) {
+  const auto& a = L.a;
   int rc;
   int32_t syncs = 0, enqueued = 0;
   auto look = [&]() -> int {
@@ -570,23 +591,23 @@ int CgSolve(const cse::CgArgs& a, const cse_cg_options& o, cse::CgState* state_h
     return CSE_OK;
   };
   const bool zero_guess = (o.flags & CSE_CG_ZERO_INITIAL_GUESS) != 0;
-  cse::LaunchCgInit(a, zero_guess, s);
+  L.Init(zero_guess, s);
   if (!zero_guess) {
     if ((rc = op((const double*)a.x, a.tmp))) return rc;
-    cse::LaunchCgInitialResidual(a, s);
+    L.InitialResidual(s);
   }
   CSE_HIP(hipGetLastError());
   // |b| = 0 and convergence before the first iteration end here.
   if ((rc = look())) return rc;
   for (int32_t it = 1; !state_host->done && it <= o.max_num_iterations; ++it) {
-    cse::LaunchCgDirection(a, s);
+    L.Direction(s);
     if ((rc = op((const double*)a.p, a.z))) return rc;
     if (it % o.residual_reset_period == 0) {
-      cse::LaunchCgUpdate(cse::kCgUpdateX, a, s);
+      L.Update(cse::kCgUpdateX, s);
       if ((rc = op((const double*)a.x, a.tmp))) return rc;
-      cse::LaunchCgUpdate(cse::kCgUpdateReset, a, s);
+      L.Update(cse::kCgUpdateReset, s);
     } else {
-      cse::LaunchCgUpdate(cse::kCgUpdateFull, a, s);
+      L.Update(cse::kCgUpdateFull, s);
     }
     CSE_HIP(hipGetLastError());
     ++enqueued;
@@ -594,7 +615,7 @@ int CgSolve(const cse::CgArgs& a, const cse_cg_options& o, cse::CgState* state_h
       if ((rc = look())) return rc;
   }
   const cse::CgState& st = *state_host;
-  if (!st.done) return Fail(CSE_ERR_HIP, "cse_schur_solve: the device state did not terminate");
+  if (!st.done) return Fail(CSE_ERR_HIP, std::string(what) + ": the device state did not terminate");
   summary->termination_type = st.termination_type;
   summary->reason = st.reason;
   summary->num_iterations = st.iteration;
@@ -607,6 +628,144 @@ int CgSolve(const cse::CgArgs& a, const cse_cg_options& o, cse::CgState* state_h
   summary->zeta = st.zeta;
   summary->rho = st.rho;
   summary->pq = st.pq;
+  return CSE_OK;
+}
+
+// The argument checks cse_schur_solve and cse_cgnr_solve share.
+int CgArgumentCheck(const char* what, const cse_cg_options* options, const double* d_rhs, const double* d_x,
+                    const cse_cg_summary* summary) {
+  const std::string w = std::string(what) + ": ";
+  if (!options || !summary || !d_rhs || !d_x)
+    return Fail(CSE_ERR_INVALID, w + "null options, summary, d_rhs or d_x");
+  const cse_cg_options& o = *options;
+  if (o.check_period < 1) return Fail(CSE_ERR_INVALID, w + "check_period is below 1");
+  if (o.residual_reset_period < 1) return Fail(CSE_ERR_INVALID, w + "residual_reset_period is below 1");
+  if (o.max_num_iterations < 1) return Fail(CSE_ERR_INVALID, w + "max_num_iterations is below 1");
+  if (o.min_num_iterations < 0) return Fail(CSE_ERR_INVALID, w + "min_num_iterations is negative");
+  if (o.reserved != 0) return Fail(CSE_ERR_INVALID, w + "options.reserved is not 0");
+  if (o.flags & ~CSE_CG_ZERO_INITIAL_GUESS) return Fail(CSE_ERR_INVALID, w + "unknown flags");
+  return CSE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// CGNR on the device: the block-Jacobi preconditioner (cgnr_kernels.hpp) and
+// cse_cgnr_solve (cg_sliced_kernels.hpp through cg_kernels.h)
+// ---------------------------------------------------------------------------
+// The Gram of slot j through its gradient plan, in the plan's form (as
+// LaunchColumnNormSlot).  values: the S x S block of the plan's first
+// parameter block; partial: cse_cgnr_init's own chunk partials.
+template <int NR, int S>
+void LaunchGramSlot(const cse::GradArgs& ga, const Group::GradPlan& P, double* values, double* partial,
+                    hipStream_t s) {
+  if (ga.count <= 0) return;
+  if (ga.perm == nullptr) {
+    hipLaunchKernelGGL((cse::GramRangeKernel<NR, S>), dim3((unsigned)((ga.count + cse::kWave - 1) / cse::kWave)),
+                       dim3(cse::kWave), 0, s, ga, values);
+  } else if (P.wave) {
+    const cse::GradChunks ch{P.chunk_begin.p, P.chunk_off.p, partial, P.nchunks};
+    if (P.nchunks > 0)
+      hipLaunchKernelGGL((cse::GramLanesKernel<NR, S>),
+                         dim3((unsigned)((P.nchunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
+                         dim3(cse::kBlockThreads), 0, s, ga, ch);
+    hipLaunchKernelGGL((cse::GramChunkReduceKernel<S>),
+                       dim3((unsigned)((ga.count + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                       dim3(cse::kBlockThreads), 0, s, ga, ch, values);
+  } else {
+    hipLaunchKernelGGL((cse::GramSlotKernel<NR, S>),
+                       dim3((unsigned)((ga.count + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                       dim3(cse::kBlockThreads), 0, s, ga, values);
+  }
+}
+
+template <int NR>
+void LaunchGramSize(int size, const cse::GradArgs& ga, const Group::GradPlan& P, double* values,
+                    double* partial, hipStream_t s) {
+  switch (size) {
+    case 1: LaunchGramSlot<NR, 1>(ga, P, values, partial, s); break;
+    case 2: LaunchGramSlot<NR, 2>(ga, P, values, partial, s); break;
+    case 3: LaunchGramSlot<NR, 3>(ga, P, values, partial, s); break;
+    case 4: LaunchGramSlot<NR, 4>(ga, P, values, partial, s); break;
+    case 5: LaunchGramSlot<NR, 5>(ga, P, values, partial, s); break;
+    case 6: LaunchGramSlot<NR, 6>(ga, P, values, partial, s); break;
+    case 7: LaunchGramSlot<NR, 7>(ga, P, values, partial, s); break;
+    case 8: LaunchGramSlot<NR, 8>(ga, P, values, partial, s); break;
+    case 9: LaunchGramSlot<NR, 9>(ga, P, values, partial, s); break;
+    case 10: LaunchGramSlot<NR, 10>(ga, P, values, partial, s); break;
+    default: break;  // ColumnNormShape
+  }
+}
+
+void LaunchGramPass(int nr, int size, const cse::GradArgs& ga, const Group::GradPlan& P, double* values,
+                    double* partial, hipStream_t s) {
+  if (nr == 1) LaunchGramSize<1>(size, ga, P, values, partial, s);
+  if (nr == 2) LaunchGramSize<2>(size, ga, P, values, partial, s);
+  if (nr == 3) LaunchGramSize<3>(size, ga, P, values, partial, s);
+}
+
+// An affine group's Gram goes through its gradient plans when every slot has
+// one in a form the kernels take (as the column norm) and its parameter blocks
+// are consecutive entries of the block table (CgnrUpload's value_base).
+bool GramThroughPlans(const cse_evaluator* ev, size_t gi) {
+  const Group& G = ev->groups[gi];
+  if (!G.affine || G.const0) return false;
+  const int sizes[2] = {G.shape.s0, G.shape.s1};
+  for (int j = 0; j < G.shape.nb; ++j) {
+    const Group::GradPlan& P = G.grad[j];
+    if (j >= 2 || !P.ready || !ColumnNormShape(G.shape.nr, sizes[j])) return false;
+    if (!P.sorted && P.wave && !(P.chunk_begin.p && P.chunk_off.p)) return false;
+    if (ev->cgnr.value_base[2 * gi + j] < 0) return false;
+  }
+  return true;
+}
+
+// First JACOBI init: every affine slot's first block is looked up in the
+// plan's runs, and the table is expanded and uploaded (the host copy lives
+// for this call only).
+int CgnrUpload(cse_evaluator* ev) {
+  auto& C = ev->cgnr;
+  if (C.uploaded) return CSE_OK;
+  C.value_base.assign(2 * ev->groups.size(), -1);
+  int64_t chunk_doubles = 1;
+  for (size_t gi = 0; gi < ev->groups.size(); ++gi) {
+    const Group& G = ev->groups[gi];
+    if (!G.affine || G.const0) continue;
+    const int sizes[2] = {G.shape.s0, G.shape.s1};
+    for (int j = 0; j < G.shape.nb && j < 2; ++j) {
+      const Group::GradPlan& P = G.grad[j];
+      if (!P.ready || P.count <= 0) continue;
+      const int S = sizes[j];
+      // Blocks lo .. lo + count - 1 are consecutive entries of size S when
+      // the first is in a run of that size that holds count more.
+      const cse::CgnrRun* run = nullptr;
+      const int64_t first = cse::FindCgnrBlock(C.plan, G.delta_base[j] + (int64_t)S * P.lo, &run);
+      if (first < 0 || run->tangent_size != S || first + P.count > run->first_block + run->count) continue;
+      C.value_base[2 * gi + j] = run->value_offset + (first - run->first_block) * (int64_t)S * S;
+      if (P.wave) chunk_doubles = std::max<int64_t>(chunk_doubles, P.nchunks * cse::GramCount(S));
+    }
+  }
+  int rc;
+  if ((rc = C.chunk_partial.ensure((size_t)chunk_doubles))) return rc;
+  if ((rc = C.values.ensure((size_t)std::max<int64_t>(C.plan.num_values, 1)))) return rc;
+  std::vector<cse::CgnrBlock> table;
+  try {
+    cse::ExpandCgnrBlocks(C.plan, &table);
+  } catch (const std::bad_alloc&) {
+    return Fail(CSE_ERR_OOM, "cse_cgnr_init: host allocation of the block table failed");
+  }
+  if ((rc = C.blocks.upload(table.data(), table.size(), ev->stream))) return rc;
+  // The copy reads the host table: wait before it goes out of scope.
+  CSE_HIP(hipStreamSynchronize(ev->stream));
+  C.ntab = (int64_t)table.size();
+  C.uploaded = true;
+  return CSE_OK;
+}
+
+int CgnrCheck(cse_evaluator* ev, const char* what, bool need_ready) {
+  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
+  CSE_SINGLE_DEVICE(ev, what);
+  if (!ev->has_layout) return Fail(CSE_ERR_INVALID, "the descriptor had no Jacobian layout");
+  if (need_ready && !ev->cgnr.ready) return Fail(CSE_ERR_INVALID, std::string(what) + ": cse_cgnr_init has not run");
+  CSE_HIP(hipSetDevice(ev->device));
   return CSE_OK;
 }
 
@@ -935,20 +1094,10 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
                     const double* d_rhs, double* d_x, double* d_step, cse_cg_summary* summary) {
   if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
   CSE_SINGLE_DEVICE(ev, "cse_schur_solve");
-  if (!options || !summary || !d_rhs || !d_x)
-    return Fail(CSE_ERR_INVALID, "cse_schur_solve: null options, summary, d_rhs or d_x");
-  const cse_cg_options& o = *options;
-  if (o.check_period < 1) return Fail(CSE_ERR_INVALID, "cse_schur_solve: check_period is below 1");
-  if (o.residual_reset_period < 1)
-    return Fail(CSE_ERR_INVALID, "cse_schur_solve: residual_reset_period is below 1");
-  if (o.max_num_iterations < 1)
-    return Fail(CSE_ERR_INVALID, "cse_schur_solve: max_num_iterations is below 1");
-  if (o.min_num_iterations < 0)
-    return Fail(CSE_ERR_INVALID, "cse_schur_solve: min_num_iterations is negative");
-  if (o.reserved != 0) return Fail(CSE_ERR_INVALID, "cse_schur_solve: options.reserved is not 0");
-  if (o.flags & ~CSE_CG_ZERO_INITIAL_GUESS) return Fail(CSE_ERR_INVALID, "cse_schur_solve: unknown flags");
-  int rc = SchurCheck(ev, true);
+  int rc = CgArgumentCheck("cse_schur_solve", options, d_rhs, d_x, summary);
   if (rc) return rc;
+  const cse_cg_options& o = *options;
+  if ((rc = SchurCheck(ev, true))) return rc;
   auto& S = ev->schur;
   const int64_t n = S.f_cols;
   if (d_rhs < d_x + n && d_x < d_rhs + n) return Fail(CSE_ERR_INVALID, "cse_schur_solve: d_x overlaps d_rhs");
@@ -986,15 +1135,154 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
   a.params = cse::CgParams{o.min_num_iterations, o.max_num_iterations, o.r_tolerance, o.q_tolerance};
   std::memset(summary, 0, sizeof(*summary));
   if (d_S_values)
-    rc = CgSolve(a, o, W.state_host, ev->stream,
+    rc = CgSolve("cse_schur_solve", SchurCgLaunch{a}, o, W.state_host, ev->stream,
                  [&](const double* x, double* y) { return cse_schur_explicit_multiply(ev, d_S_values, x, y); },
                  summary);
   else
-    rc = CgSolve(a, o, W.state_host, ev->stream,
+    rc = CgSolve("cse_schur_solve", SchurCgLaunch{a}, o, W.state_host, ev->stream,
                  [&](const double* x, double* y) { return cse_schur_multiply(ev, x, y); }, summary);
   if (rc) return rc;
   if (d_step && summary->termination_type != CSE_CG_FAILURE) return cse_schur_back_substitute(ev, d_x, d_step);
   return CSE_OK;
+}
+
+int cse_cgnr_init(cse_evaluator* ev, const double* d_jacobian_values, const double* d_D, const double* d_b,
+                  double* d_rhs, int preconditioner) {
+  int rc = CgnrCheck(ev, "cse_cgnr_init", false);
+  if (rc) return rc;
+  if (!d_jacobian_values) return Fail(CSE_ERR_INVALID, "cse_cgnr_init: null d_jacobian_values");
+  if ((d_b == nullptr) != (d_rhs == nullptr))
+    return Fail(CSE_ERR_INVALID, "cse_cgnr_init: d_b and d_rhs go together (both NULL, or both given)");
+  if (preconditioner != CSE_CGNR_IDENTITY && preconditioner != CSE_CGNR_JACOBI)
+    return Fail(CSE_ERR_INVALID, "cse_cgnr_init: unknown preconditioner");
+  auto& C = ev->cgnr;
+  if (preconditioner == CSE_CGNR_JACOBI) {
+    if (!C.plan.tiles)
+      return Fail(CSE_ERR_UNSUPPORTED,
+                  "cse_cgnr_init: JACOBI needs the non-constant parameter blocks to tile "
+                  "[0, num_effective_parameters) exactly (a gap or an overlap in the delta offsets)");
+    if (!C.plan.fits)
+      return Fail(CSE_ERR_UNSUPPORTED, "cse_cgnr_init: JACOBI takes blocks of at most " +
+                                           std::to_string(cse::kCgnrMaxBlockColumns) +
+                                           " tangent columns; the largest here has " +
+                                           std::to_string(C.plan.max_size));
+  }
+  hipStream_t s = ev->stream;
+  C.ready = false;
+  if (d_rhs) {
+    // rhs = J^T b (cgnr_solver.cc:365-367).
+    if (ev->num_effective > 0) CSE_HIP(hipMemsetAsync(d_rhs, 0, ev->num_effective * sizeof(double), s));
+    if ((rc = JacobianMultiply(ev, d_jacobian_values, d_b, d_rhs, true))) return rc;
+  }
+  if (preconditioner == CSE_CGNR_JACOBI) {
+    if ((rc = CgnrUpload(ev))) return rc;
+    // The status word read by cse_wait reports a pivot that is not positive.
+    CSE_HIP(hipMemsetAsync(ev->status.p + 1, 0, sizeof(int), s));
+    // Zero, then every group adds its cells' J^T J in group order.
+    CSE_HIP(hipMemsetAsync(C.values.p, 0, C.values.n * sizeof(double), s));
+    for (size_t gi = 0; gi < ev->groups.size(); ++gi) {
+      Group& G = ev->groups[gi];
+      if (G.n == 0) continue;
+      if (GramThroughPlans(ev, gi)) {
+        const int sizes[2] = {G.shape.s0, G.shape.s1};
+        for (int j = 0; j < G.shape.nb; ++j)
+          LaunchGramPass(G.shape.nr, sizes[j], SlotGradArgs(G, j, d_jacobian_values, nullptr, nullptr), G.grad[j],
+                         C.values.p + C.value_base[2 * gi + j], C.chunk_partial.p, s);
+      } else {
+        const bool affine = G.affine && !G.const0;
+        if (!affine && !ev->any_general)
+          return Fail(CSE_ERR_UNSUPPORTED, "table-path tables were not uploaded");
+        const cse::ColumnBlockArgs a = MakeColumnBlockArgs(ev, G, affine);
+        hipLaunchKernelGGL(cse::GramBlockKernel, dim3((unsigned)((a.n + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                           dim3(cse::kBlockThreads), 0, s, a, d_jacobian_values, C.blocks.p, C.ntab, C.values.p);
+      }
+      CSE_HIP(hipGetLastError());
+    }
+    if (C.ntab > 0) {
+      const dim3 grid((unsigned)((C.ntab + cse::kWave - 1) / cse::kWave));
+      if (C.plan.max_size > 10)
+        hipLaunchKernelGGL(cse::CgnrInvertKernel<true>, grid, dim3(cse::kWave), 0, s, C.blocks.p, C.ntab, d_D,
+                           C.values.p, ev->status.p + 1);
+      else
+        hipLaunchKernelGGL(cse::CgnrInvertKernel<false>, grid, dim3(cse::kWave), 0, s, C.blocks.p, C.ntab, d_D,
+                           C.values.p, ev->status.p + 1);
+      CSE_HIP(hipGetLastError());
+    }
+  }
+  C.jac = d_jacobian_values;
+  C.D = d_D;
+  C.preconditioner = preconditioner;
+  C.ready = true;
+  return CSE_OK;
+}
+
+int cse_cgnr_precondition(cse_evaluator* ev, const double* d_x, double* d_y) {
+  int rc = CgnrCheck(ev, "cse_cgnr_precondition", true);
+  if (rc) return rc;
+  if (!d_x || !d_y) return Fail(CSE_ERR_INVALID, "cse_cgnr_precondition: null pointer");
+  const int64_t n = ev->num_effective;
+  if (d_x < d_y + n && d_y < d_x + n) return Fail(CSE_ERR_INVALID, "cse_cgnr_precondition: x and y overlap");
+  const auto& C = ev->cgnr;
+  hipStream_t s = ev->stream;
+  if (C.preconditioner == CSE_CGNR_IDENTITY) {  // CudaIdentityPreconditioner: y += x
+    if (n > 0)
+      hipLaunchKernelGGL(cse::AxpyKernel, dim3((unsigned)((n + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                         dim3(cse::kBlockThreads), 0, s, d_x, d_y, n);
+  } else {
+    cse::LaunchCgnrApplyBlocks(C.blocks.p, C.ntab, C.values.p, d_x, d_y, false, nullptr, s);
+  }
+  CSE_HIP(hipGetLastError());
+  return CSE_OK;
+}
+
+int cse_cgnr_solve(cse_evaluator* ev, const cse_cg_options* options, const double* d_rhs, double* d_x,
+                   cse_cg_summary* summary) {
+  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
+  CSE_SINGLE_DEVICE(ev, "cse_cgnr_solve");
+  int rc = CgArgumentCheck("cse_cgnr_solve", options, d_rhs, d_x, summary);
+  if (rc) return rc;
+  const cse_cg_options& o = *options;
+  if ((rc = CgnrCheck(ev, "cse_cgnr_solve", true))) return rc;
+  const int64_t n = ev->num_effective;
+  if (d_rhs < d_x + n && d_x < d_rhs + n) return Fail(CSE_ERR_INVALID, "cse_cgnr_solve: d_x overlaps d_rhs");
+  auto& C = ev->cgnr;
+  auto& W = ev->cg;
+  const int64_t nslices = cse::CgSliceCount(n);
+  if ((rc = C.vectors.ensure((size_t)4 * (size_t)std::max<int64_t>(n, 1)))) return rc;
+  if ((rc = C.partial.ensure((size_t)(2 * nslices)))) return rc;
+  if (!C.counter.p) {
+    if ((rc = C.counter.alloc(1))) return rc;
+    CSE_HIP(hipMemsetAsync(C.counter.p, 0, sizeof(int), ev->stream));
+  }
+  if ((rc = W.state.ensure(1))) return rc;
+  if (!W.state_host) CSE_HIP(hipHostMalloc((void**)&W.state_host, sizeof(cse::CgState)));
+  cse::CgSlicedArgs a{};
+  a.n = n;
+  a.rhs = d_rhs;
+  a.x = d_x;
+  a.p = C.vectors.p;
+  a.r = a.p + n;
+  a.z = a.r + n;
+  a.tmp = a.z + n;
+  a.zr = a.r;
+  if (C.preconditioner == CSE_CGNR_JACOBI) {
+    a.zr = a.z;
+    a.tab = C.blocks.p;
+    a.ntab = C.ntab;
+    a.precond = C.values.p;
+  }
+  a.state = W.state.p;
+  a.params = cse::CgParams{o.min_num_iterations, o.max_num_iterations, o.r_tolerance, o.q_tolerance};
+  a.partial = C.partial.p;
+  a.counter = C.counter.p;
+  std::memset(summary, 0, sizeof(*summary));
+  // CudaCgnrLinearOperator (cgnr_solver.cc:226-237) accumulates: y is zeroed first.
+  return CgSolve("cse_cgnr_solve", CgnrCgLaunch{a}, o, W.state_host, ev->stream,
+                 [&](const double* x, double* y) -> int {
+                   if (n > 0) CSE_HIP(hipMemsetAsync(y, 0, n * sizeof(double), ev->stream));
+                   return cse_cgnr_multiply(ev, C.jac, C.D, x, y);
+                 },
+                 summary);
 }
 
 }  // extern "C"

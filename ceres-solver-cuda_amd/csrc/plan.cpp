@@ -996,6 +996,79 @@ void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* 
   }
 }
 
+void PlanCgnrBlocks(const cse_problem_desc* d, CgnrBlockPlan* plan) {
+  *plan = CgnrBlockPlan{};
+  int64_t next = 0;
+  bool tiles = true;
+  auto add = [&](int64_t delta, int32_t size) {
+    tiles = tiles && delta == next;
+    auto& R = plan->runs;
+    if (!R.empty() && R.back().tangent_size == size &&
+        R.back().delta_offset + R.back().count * size == delta && delta == next)
+      ++R.back().count;
+    else
+      R.push_back({delta, plan->num_values, plan->num_blocks, 1, size, 0});
+    next = delta + size;
+    ++plan->num_blocks;
+    plan->num_values += (int64_t)size * size;
+    plan->max_size = std::max(plan->max_size, (int)size);
+  };
+  // A program's blocks come in delta order as a rule (4.4 million at
+  // problem-13682): one pass, nothing stored but the runs.
+  bool sorted = true;
+  int64_t last = -1;
+  for (int64_t b = 0; b < d->num_parameter_blocks && sorted; ++b) {
+    const cse_parameter_block& pb = d->parameter_blocks[b];
+    if (pb.is_constant || pb.tangent_size <= 0) continue;
+    sorted = pb.delta_offset >= last;
+    last = pb.delta_offset;
+    if (sorted) add(pb.delta_offset, pb.tangent_size);
+  }
+  if (!sorted) {
+    // Out of order: the blocks are listed, sorted and run through again.
+    *plan = CgnrBlockPlan{};
+    next = 0;
+    tiles = true;
+    std::vector<std::pair<int64_t, int32_t>> all;
+    for (int64_t b = 0; b < d->num_parameter_blocks; ++b) {
+      const cse_parameter_block& pb = d->parameter_blocks[b];
+      if (!pb.is_constant && pb.tangent_size > 0) all.emplace_back(pb.delta_offset, pb.tangent_size);
+    }
+    std::stable_sort(all.begin(), all.end(),
+                     [](const std::pair<int64_t, int32_t>& x, const std::pair<int64_t, int32_t>& y) {
+                       return x.first < y.first;
+                     });
+    for (const auto& e : all) add(e.first, e.second);
+  }
+  plan->tiles = tiles && next == d->num_effective_parameters;
+  plan->fits = plan->max_size <= kCgnrMaxBlockColumns;
+}
+
+void ExpandCgnrBlocks(const CgnrBlockPlan& plan, std::vector<CgnrBlock>* blocks) {
+  blocks->clear();
+  blocks->reserve((size_t)plan.num_blocks);
+  for (const CgnrRun& r : plan.runs) {
+    const int64_t s = r.tangent_size;
+    for (int64_t k = 0; k < r.count; ++k)
+      blocks->push_back({r.delta_offset + k * s, r.value_offset + k * s * s, r.tangent_size, 0});
+  }
+}
+
+int64_t FindCgnrBlock(const CgnrBlockPlan& plan, int64_t delta, const CgnrRun** run) {
+  const auto& R = plan.runs;
+  // The last run that starts at or before delta.
+  auto it = std::upper_bound(R.begin(), R.end(), delta,
+                             [](int64_t v, const CgnrRun& x) { return v < x.delta_offset; });
+  if (it == R.begin()) return -1;
+  --it;
+  // Runs of equal start (overlapping blocks, no tiling): the first of them.
+  while (it != R.begin() && (it - 1)->delta_offset == it->delta_offset) --it;
+  const int64_t k = delta - it->delta_offset;
+  if (k % it->tangent_size != 0 || k / it->tangent_size >= it->count) return -1;
+  if (run) *run = &*it;
+  return it->first_block + k / it->tangent_size;
+}
+
 int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPlan* plan) {
   *plan = SchurPairPlan{};
   if (n >= ((int64_t)1 << 31))

@@ -273,6 +273,43 @@ void PlanGroup(const cse_problem_desc* d, const cse_options& opts, int gi, Progr
 void PlanProgram(const cse_problem_desc* d, const GroupPlan* only, ProgramPlan* P,
                  const GroupTables* only_tables = nullptr);
 
+// ---- cse_cgnr_init's block-Jacobi preconditioner: one entry per non-constant
+// parameter block with columns, sorted by delta_offset; value_offset is the
+// running sum of tangent_size^2 (packed row-major blocks,
+// BlockCRSJacobiPreconditioner's storage, block_jacobi_preconditioner.cc:135-170).
+// Needs only the descriptor's parameter blocks and num_effective_parameters.
+// cse_create keeps the table as runs -- consecutive entries of one size whose
+// columns follow each other (two runs for a BAL problem: the points, the
+// cameras) -- so that a program that never asks for JACOBI pays a pass over its
+// parameter blocks and a few bytes; the first JACOBI init expands them
+// (ExpandCgnrBlocks: 24 bytes per block, 107 MB at problem-13682), uploads the
+// table and drops it.
+struct CgnrRun {
+  int64_t delta_offset;  // of the run's first block
+  int64_t value_offset;
+  int64_t first_block;   // its index in the table
+  int64_t count;
+  int32_t tangent_size;
+  int32_t pad;
+};
+struct CgnrBlockPlan {
+  std::vector<CgnrRun> runs;
+  int64_t num_blocks = 0;
+  int64_t num_values = 0;  // sum of tangent_size^2
+  int max_size = 0;        // largest tangent_size
+  // JACOBI needs both: the blocks tile [0, num_effective_parameters) exactly
+  // (no gap, no overlap), and none has more than kCgnrMaxBlockColumns columns.
+  bool tiles = false;
+  bool fits = false;
+};
+void PlanCgnrBlocks(const cse_problem_desc* d, CgnrBlockPlan* plan);
+// The table itself, num_blocks entries.
+void ExpandCgnrBlocks(const CgnrBlockPlan& plan, std::vector<CgnrBlock>* blocks);
+// The index of the entry whose delta_offset is `delta`, or -1; *run (may be
+// null) receives its run.  For a plan that tiles (runs that overlap may hide
+// an entry; JACOBI refuses such a plan before any lookup).
+int64_t FindCgnrBlock(const CgnrBlockPlan& plan, int64_t delta, const CgnrRun** run = nullptr);
+
 // ---- The explicit Schur complement's pair plan (cse_schur_complement): which
 // residual-block pairs add into which 9 x 9 block of S.  Host only; built on
 // the first cse_schur_complement or cse_schur_complement_plan call, never by

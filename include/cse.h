@@ -675,6 +675,60 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options,
                     const double* d_S_values, const double* d_rhs, double* d_x,
                     double* d_step, cse_cg_summary* summary);
 
+/* ---- CGNR on the device --------------------------------------------------
+ * CudaCgnrSolver (internal/ceres/cgnr_solver.cc:218-387), the one linear
+ * solver the reference runs on the GPU, over this evaluator's Jacobian values
+ * in HBM: the operator (cse_cgnr_multiply = CudaCgnrLinearOperator, :218-243),
+ * an IDENTITY or JACOBI preconditioner (:245-280), the right-hand side A^T b
+ * (:365-367) and ConjugateGradientsSolver over four scratch vectors (:375-383).
+ * Every single-device evaluator with a Jacobian layout is served -- several
+ * groups, the table path, any shape, held blocks, both layouts: whatever
+ * cse_cgnr_multiply serves.
+ *
+ * JACOBI is BlockCRSJacobiPreconditioner (block_jacobi_preconditioner.cc:
+ * 116-224): per non-constant parameter block the tangent_size x tangent_size
+ * matrix (sum over its cells of J_cell^T J_cell + diag(D^2))^-1 by Cholesky
+ * (:208-221), stored as packed row-major blocks in delta-offset order (:133-145).
+ * The reference computes it on the CPU and copies it over on every solve
+ * (cgnr_solver.cc:267-270); here it is built on the device from the values.
+ * Deterministic on affine groups with gradient plans (each parameter block adds
+ * its cells in the plan's fixed order, the groups in group order); FP64 atomics
+ * for every other group, the split cse_jacobian_squared_column_norm has.  A
+ * block whose pivot is not positive and finite (an unobserved block with
+ * D = NULL) is left zero and the next cse_wait returns CSE_EVALUATION_FAILED,
+ * as cse_schur_init documents.  JACOBI is refused (CSE_ERR_UNSUPPORTED) when
+ * the non-constant blocks do not tile [0, num_effective_parameters) exactly or
+ * one has more than 16 tangent columns; IDENTITY never is. */
+enum cse_cgnr_preconditioner { CSE_CGNR_IDENTITY = 0, CSE_CGNR_JACOBI = 1 };
+
+/* Binds J and D (D may be NULL; both must stay valid until the next init).
+ * d_b / d_rhs: both NULL, or rhs = J^T b assigned (d_b: num_residuals, d_rhs:
+ * num_effective_parameters; cgnr_solver.cc:365-367).  JACOBI: builds the
+ * block-diagonal inverse described above.  Asynchronous on the evaluator's
+ * stream.  CSE_ERR_INVALID: a NULL evaluator or d_jacobian_values, one of
+ * d_b / d_rhs alone, an unknown preconditioner, no Jacobian layout. */
+int cse_cgnr_init(cse_evaluator* ev, const double* d_jacobian_values, const double* d_D,
+                  const double* d_b, double* d_rhs, int preconditioner);
+
+/* y += M^-1 x, num_effective_parameters entries (IDENTITY: y += x;
+ * cgnr_solver.cc:249-251, :272-274).  x and y may not overlap.  Needs
+ * cse_cgnr_init. */
+int cse_cgnr_precondition(cse_evaluator* ev, const double* d_x, double* d_y);
+
+/* (J^T J + D^2) x = rhs by the reference's ConjugateGradientsSolver
+ * (conjugate_gradients_solver.h:108-305), every vector, scalar and stopping
+ * test on the device, as cse_schur_solve: the same options, summary and
+ * CSE_CG_ZERO_INITIAL_GUESS, the same argument checks, CSE_OK for every
+ * termination type, deterministic and independent of check_period.  d_rhs,
+ * d_x: num_effective_parameters entries that do not overlap.  CSE_ERR_INVALID
+ * without a prior cse_cgnr_init; CSE_ERR_UNSUPPORTED on a cse_create_multi
+ * handle.  The vector kernels are sliced (one workgroup per 2048 entries, the
+ * slice sums combined in a fixed order by the workgroup that finishes last);
+ * four num_effective_parameters vectors, the slice partials and the state are
+ * allocated by the first call and kept. */
+int cse_cgnr_solve(cse_evaluator* ev, const cse_cg_options* options, const double* d_rhs,
+                   double* d_x, cse_cg_summary* summary);
+
 /* ---- One host solve, several GPUs --------------------------------------
  * The reference evaluates on one device (ContextImpl's single stream,
  * include/ceres/internal/cuda_buffer.h:98) and Ceres' host solve calls one
