@@ -60,6 +60,7 @@ FUNCTOR_SHAPES = {
 SCHUR_IDENTITY = 0
 SCHUR_JACOBI = 1
 SCHUR_SCHUR_JACOBI = 2
+SCHUR_POWER_SERIES_EXPANSION = 3
 
 # cse_cgnr_preconditioner
 CGNR_IDENTITY = 0
@@ -166,6 +167,11 @@ class cse_cg_summary(C.Structure):
                 ("zeta", C.c_double), ("rho", C.c_double), ("pq", C.c_double)]
 
 
+class cse_spse_summary(C.Structure):
+    _fields_ = [("num_terms", C.c_int32), ("reserved", C.c_int32),
+                ("norm_first", C.c_double), ("norm_last", C.c_double)]
+
+
 P_i32 = C.POINTER(C.c_int32)
 P_i64 = C.POINTER(C.c_int64)
 P_f64 = C.POINTER(C.c_double)
@@ -199,6 +205,9 @@ SIGNATURES = {
     "cse_schur_multiply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cse_schur_precondition": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cse_schur_back_substitute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cse_schur_power_series": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.POINTER(cse_spse_summary)]),
+    "cse_schur_set_spse_iterations": (C.c_int, [C.c_void_p, C.c_int32]),
     "cse_schur_complement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "cse_schur_complement_plan": (C.c_int, [C.c_void_p, P_i64, P_i64, P_i64]),
     "cse_schur_complement_sparse_structure": (C.c_int, [C.c_void_p, P_i64, P_i64, P_i64, P_i64, P_i32]),

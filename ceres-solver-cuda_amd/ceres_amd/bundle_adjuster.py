@@ -70,8 +70,22 @@ def parse(argv=None):
                          "instead of on the implicit operator.  Not a faster solve on the shapes measured "
                          "(level at 49 cameras, slower beyond): see DESIGN 3.6b")
     ap.add_argument("--preconditioner", default="jacobi",
-                    choices=["identity", "jacobi", "schur_jacobi"],
-                    help="iterative_schur's preconditioner (bundle_adjuster.cc default: jacobi)")
+                    choices=["identity", "jacobi", "schur_jacobi", "schur_power_series_expansion"],
+                    help="iterative_schur's preconditioner (bundle_adjuster.cc default: jacobi); "
+                         "schur_power_series_expansion: --max_num_spse_iterations terms of the series "
+                         "of S^-1 per application (cse_schur_power_series), in the host loop and with "
+                         "--device_pcg; not with --use_explicit_schur_complement, as the reference")
+    ap.add_argument("--max_num_spse_iterations", type=int, default=5,
+                    help="terms of the power series, for the preconditioner and for "
+                         "--use_spse_initialization (bundle_adjuster.cc's flag)")
+    ap.add_argument("--use_spse_initialization", action="store_true",
+                    help="iterative_schur only (Solver::Options::use_spse_initialization): start the PCG "
+                         "from x0 = the power series of S^-1 applied to the right-hand side, up to "
+                         "--max_num_spse_iterations terms or until a term's norm is below "
+                         "--spse_tolerance of the first; with every preconditioner and with held cameras")
+    ap.add_argument("--spse_tolerance", type=float, default=0.1,
+                    help="--use_spse_initialization: stop the series at a term below this fraction of "
+                         "the zeroth term's norm")
     ap.add_argument("--device_pcg", action="store_true",
                     help="iterative_schur only: the whole PCG as one call (cse_schur_solve: the "
                          "reference's ConjugateGradientsSolver with its vectors, scalars and stopping "
@@ -128,6 +142,21 @@ def parse(argv=None):
     if args.use_explicit_schur_complement and args.linear_solver != "iterative_schur":
         raise SystemExit("--use_explicit_schur_complement needs --linear_solver iterative_schur, not "
                          f"{args.linear_solver}")
+    series_pre = args.preconditioner == "schur_power_series_expansion"
+    if (args.use_spse_initialization or series_pre) and args.linear_solver != "iterative_schur":
+        raise SystemExit("--use_spse_initialization and --preconditioner schur_power_series_expansion need "
+                         f"--linear_solver iterative_schur, not {args.linear_solver}")
+    if args.use_spse_initialization and args.use_explicit_schur_complement:
+        raise SystemExit("use_explicit_schur_complement does not support use_spse_initialization")
+    if series_pre and args.use_explicit_schur_complement:
+        raise SystemExit("use_explicit_schur_complement only supports SCHUR_JACOBI as the preconditioner, "
+                         "not schur_power_series_expansion")
+    if args.use_spse_initialization or series_pre:
+        # solver.cc:277-281
+        if args.max_num_spse_iterations < 1:
+            raise SystemExit("--max_num_spse_iterations must be at least 1")
+        if not (0.0 <= args.spse_tolerance < float("inf")):
+            raise SystemExit("--spse_tolerance must be finite and not negative")
     if args.device_pcg and args.linear_solver != "iterative_schur":
         raise SystemExit(f"--device_pcg needs --linear_solver iterative_schur, not {args.linear_solver}")
     if args.pcg_termination == "quadratic" and not args.device_pcg:
@@ -303,7 +332,10 @@ def solve(args, stats=None):
     if args.linear_solver != "cgnr":
         e_cols, f_cols = ev.schur_structure()
         pre = {"identity": ca._cse.SCHUR_IDENTITY, "jacobi": ca._cse.SCHUR_JACOBI,
-               "schur_jacobi": ca._cse.SCHUR_SCHUR_JACOBI}[args.preconditioner]
+               "schur_jacobi": ca._cse.SCHUR_SCHUR_JACOBI,
+               "schur_power_series_expansion": ca._cse.SCHUR_POWER_SERIES_EXPANSION}[args.preconditioner]
+        if pre == ca._cse.SCHUR_POWER_SERIES_EXPANSION:
+            ev.schur_set_spse_iterations(args.max_num_spse_iterations)
         rhs = torch.empty(f_cols, dtype=f64, device=dev)
         neg_r = torch.empty(m, dtype=f64, device=dev)
     if args.linear_solver == "dense_schur":
@@ -343,7 +375,8 @@ def solve(args, stats=None):
                                             residual_reset_period=max_it + 1)
         cg_options.max_num_iterations = max_it
         cg_options.check_period = args.pcg_check_period
-        cg_options.flags = ca._cse.CG_ZERO_INITIAL_GUESS
+        # use_spse_initialization: the PCG starts from the series' x0.
+        cg_options.flags = 0 if args.use_spse_initialization else ca._cse.CG_ZERO_INITIAL_GUESS
 
     def schur_solve(lam):
         # IterativeSchurComplementSolver (iterative_schur_complement_solver.cc:
@@ -361,14 +394,27 @@ def solve(args, stats=None):
             # ConjugateGradientsSolver and BackSubstitute in one call; the zero
             # start as IterativeSchurComplementSolver's.
             dx = torch.empty(n, dtype=f64, device=dev)
+            if args.use_spse_initialization:
+                ev.schur_power_series_device(rhs.data_ptr(), xf_device.data_ptr(),
+                                             args.max_num_spse_iterations, args.spse_tolerance)
             summary = ev.schur_solve_device(
                 rhs.data_ptr(), xf_device.data_ptr(), cg_options,
                 S_values.data_ptr() if args.use_explicit_schur_complement else None, dx.data_ptr())
             if summary.termination_type == ca._cse.CG_FAILURE:
                 raise SystemExit(f"device PCG failed (reason {summary.reason})")
             return dx, summary.num_iterations
-        xf = torch.zeros(f_cols, dtype=f64, device=dev)
-        res = rhs.clone()
+        if args.use_spse_initialization:
+            # x0 = the series of S^-1 on rhs (iterative_schur_complement_solver.cc:
+            # 108-118), r = rhs - S x0.
+            xf = torch.empty(f_cols, dtype=f64, device=dev)
+            ev.schur_power_series_device(rhs.data_ptr(), xf.data_ptr(),
+                                         args.max_num_spse_iterations, args.spse_tolerance)
+            res = torch.empty_like(xf)
+            schur_op(xf.data_ptr(), res.data_ptr())
+            res = rhs - res
+        else:
+            xf = torch.zeros(f_cols, dtype=f64, device=dev)
+            res = rhs.clone()
         z = torch.zeros_like(res)
         ev.schur_precondition_device(res.data_ptr(), z.data_ptr())
         p = z.clone()

@@ -750,6 +750,26 @@ class Evaluator:
         return _cse.check(_cse.lib().cse_schur_precondition(self.handle, d_x, d_y),
                           "cse_schur_precondition")
 
+    def schur_power_series_device(self, d_x, d_y, max_num_iterations=5, tolerance=0.0,
+                                  want_summary=False):
+        """y = sum_i (P^-1 Q)^i P^-1 x, the reference's power series expansion of
+        S^-1 (cse_schur_power_series): ASSIGNS y, where schur_precondition_device
+        accumulates.  Up to max_num_iterations terms after the zeroth, stopping
+        early once a term's norm is below tolerance * |P^-1 x| (0: never).
+        Asynchronous unless want_summary, which waits and returns the
+        _cse.cse_spse_summary (num_terms, norm_first, norm_last)."""
+        summary = _cse.cse_spse_summary() if want_summary else None
+        _cse.check(_cse.lib().cse_schur_power_series(
+            self.handle, int(max_num_iterations), float(tolerance), d_x, d_y,
+            C.byref(summary) if want_summary else None), "cse_schur_power_series")
+        return summary
+
+    def schur_set_spse_iterations(self, n):
+        """max_num_spse_iterations of the SCHUR_POWER_SERIES_EXPANSION
+        preconditioner (default 5; cse_schur_set_spse_iterations)."""
+        return _cse.check(_cse.lib().cse_schur_set_spse_iterations(self.handle, int(n)),
+                          "cse_schur_set_spse_iterations")
+
     def schur_back_substitute_device(self, d_x, d_y):
         """y = [(E^T E + D_e^2)^-1 E^T (b - F x); x] (BackSubstitute)."""
         return _cse.check(_cse.lib().cse_schur_back_substitute(self.handle, d_x, d_y),

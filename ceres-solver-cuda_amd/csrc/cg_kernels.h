@@ -1,5 +1,6 @@
 // cg_kernels.h -- the launchers of cse_schur_solve's vector kernels
-// (cg_kernels.hpp) and of cse_cgnr_solve's (cg_sliced_kernels.hpp), a
+// (cg_kernels.hpp), of cse_schur_power_series' (spse_kernels.hpp) and of
+// cse_cgnr_solve's (cg_sliced_kernels.hpp), a
 // translation unit of their own (cg_kernels.hip): it is
 // built without -ffinite-math-only, which the evaluation kernels' unit needs
 // and under which ConjugateGradientsSolver's tests for infinite scalars
@@ -13,6 +14,7 @@
 
 #include "cg_state.hpp"
 #include "host_shared.hpp"
+#include "spse_state.hpp"
 
 namespace cse {
 
@@ -39,6 +41,29 @@ void LaunchCgInit(const CgArgs& a, bool zero_guess, hipStream_t s);
 void LaunchCgInitialResidual(const CgArgs& a, hipStream_t s);
 void LaunchCgDirection(const CgArgs& a, hipStream_t s);
 void LaunchCgUpdate(CgUpdateMode mode, const CgArgs& a, hipStream_t s);
+
+// ---- cse_schur_power_series' vector kernels (spse_kernels.hpp), one workgroup
+// each as the kernels above.
+struct SpseArgs {
+  int64_t n;             // num_cols_f
+  const double* blocks;  // [pre_n / 9][9][9] inverse blocks of F^T F + D_f^2 for the
+  int64_t pre_off, pre_n;  // entries [pre_off, pre_off + pre_n); P^-1 is 0 outside them
+  const double* x;       // the zeroth kernel's input
+  double* y;             // the series' sum
+  double* prev;          // the last term
+  const double* t;       // Q prev, what the term kernel applies the blocks to
+  SpseState* state;
+  int32_t max_num_iterations;
+  double tolerance;
+};
+
+// y = P^-1 x (accumulate: y += P^-1 x), prev = that term, the state begun.
+void LaunchSpseZero(const SpseArgs& a, bool accumulate, hipStream_t s);
+// term = P^-1 t, y += term, prev = term, |term| and the stop test; nothing
+// once the state is done.
+void LaunchSpseTerm(const SpseArgs& a, hipStream_t s);
+// CgDirectionKernel with z as given (a preconditioner that wrote a.z itself).
+void LaunchCgDirectionGiven(const CgArgs& a, hipStream_t s);
 
 // ---- cse_cgnr_solve's vector kernels (cg_sliced_kernels.hpp): any length, one
 // workgroup of kCgSliceThreads lanes per slice of kCgSliceEntries entries.

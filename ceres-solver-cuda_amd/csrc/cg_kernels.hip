@@ -1,10 +1,12 @@
 // cg_kernels.hip -- cse_schur_solve's vector kernels (cg_kernels.hpp),
-// cse_cgnr_solve's (cg_sliced_kernels.hpp) and their launchers, built without
+// cse_schur_power_series' (spse_kernels.hpp), cse_cgnr_solve's
+// (cg_sliced_kernels.hpp) and their launchers, built without
 // -ffinite-math-only (cg_kernels.h says why).
 #include "cg_kernels.h"
 
 #include "cg_kernels.hpp"
 #include "cg_sliced_kernels.hpp"
+#include "spse_kernels.hpp"
 
 namespace cse {
 
@@ -30,6 +32,21 @@ void LaunchCgUpdate(CgUpdateMode mode, const CgArgs& a, hipStream_t s) {
     case kCgUpdateX: hipLaunchKernelGGL((CgUpdateKernel<kCgUpdateX>), dim3(1), dim3(kCgThreads), 0, s, a); break;
     case kCgUpdateReset: hipLaunchKernelGGL((CgUpdateKernel<kCgUpdateReset>), dim3(1), dim3(kCgThreads), 0, s, a); break;
   }
+}
+
+void LaunchSpseZero(const SpseArgs& a, bool accumulate, hipStream_t s) {
+  if (accumulate)
+    hipLaunchKernelGGL(SpseZeroKernel<true>, dim3(1), dim3(kCgThreads), 0, s, a);
+  else
+    hipLaunchKernelGGL(SpseZeroKernel<false>, dim3(1), dim3(kCgThreads), 0, s, a);
+}
+
+void LaunchSpseTerm(const SpseArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(SpseTermKernel, dim3(1), dim3(kCgThreads), 0, s, a);
+}
+
+void LaunchCgDirectionGiven(const CgArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(CgDirectionGivenKernel, dim3(1), dim3(kCgThreads), 0, s, a);
 }
 
 // One workgroup per slice.

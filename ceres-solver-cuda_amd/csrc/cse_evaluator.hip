@@ -943,6 +943,7 @@ void cse_destroy(cse_evaluator* ev) {
   if (ev->stream) (void)hipStreamSynchronize(ev->stream);
   if (ev->status_host) (void)hipHostFree(ev->status_host);
   if (ev->cg.state_host) (void)hipHostFree(ev->cg.state_host);
+  if (ev->spse.state_host) (void)hipHostFree(ev->spse.state_host);
   for (auto& pr : ev->pending) ev->pool.push_back(pr);
   for (auto& pr : ev->pool) {
     (void)hipEventDestroy(pr.first);

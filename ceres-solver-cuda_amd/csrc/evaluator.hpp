@@ -14,6 +14,7 @@
 
 #include "../../include/cse.h"
 #include "cg_state.hpp"
+#include "spse_state.hpp"
 #include "plan.hpp"
 
 struct CseMulti;  // multi_device.h
@@ -195,6 +196,10 @@ struct cse_evaluator {
     bool ready = false;
     int preconditioner = CSE_SCHUR_IDENTITY;
     const double *jac = nullptr, *D = nullptr, *b = nullptr;
+    bool ub_grad = false;  // ub holds [n][4] records (the init wrote the gradient)
+    // max_num_spse_iterations of the POWER_SERIES preconditioner
+    // (cse_schur_set_spse_iterations; linear_solver.h:172).
+    int32_t spse_iterations = 5;
     // The explicit complement's pair plan (cse::PlanSchurPairs): counted on
     // the first plan query, built and uploaded on the first
     // cse_schur_complement; structure only, so it outlives every init.
@@ -224,6 +229,18 @@ struct cse_evaluator {
     cse::DevBuf<cse::CgState> state;
     cse::CgState* state_host = nullptr;  // pinned
   } cg;
+  // cse_schur_power_series' scratch (spse_kernels.hpp), allocated by the first
+  // series: the last term and Q times it, the state, its pinned copy, and --
+  // after an init that built no (F^T F + D_f^2)^-1 blocks (IDENTITY,
+  // SCHUR_JACOBI) -- blocks of its own with the camera pass's scratch (chunk
+  // partials, the rhs and gradient rows that pass writes beside them).
+  struct Spse {
+    cse::DevBuf<double> vectors;
+    cse::DevBuf<cse::SpseState> state;
+    cse::SpseState* state_host = nullptr;  // pinned
+    cse::DevBuf<double> blocks, partial, rows;
+    bool blocks_ready = false;  // blocks are those of the current init
+  } spse;
   // CGNR on the device (cse_cgnr_init, cse_cgnr_precondition, cse_cgnr_solve).
   // `plan` is the block table as cse_create planned it from the descriptor, in
   // runs; the first JACOBI init expands it, uploads it and looks each affine

@@ -351,7 +351,7 @@ int SchurInit(cse_evaluator* ev, const double* d_jacobian_values, const double* 
   if (!d_jacobian_values || !d_b || !d_rhs) return Fail(CSE_ERR_INVALID, "null pointer");
   auto& S = ev->schur;
   if (preconditioner != CSE_SCHUR_IDENTITY && preconditioner != CSE_SCHUR_JACOBI &&
-      preconditioner != CSE_SCHUR_SCHUR_JACOBI)
+      preconditioner != CSE_SCHUR_SCHUR_JACOBI && preconditioner != CSE_SCHUR_POWER_SERIES_EXPANSION)
     return Fail(CSE_ERR_INVALID, "unknown preconditioner");
   if (preconditioner == CSE_SCHUR_SCHUR_JACOBI && S.duplicates)
     return Fail(CSE_ERR_UNSUPPORTED,
@@ -366,6 +366,8 @@ int SchurInit(cse_evaluator* ev, const double* d_jacobian_values, const double* 
   S.D = d_D;
   S.b = d_b;
   S.preconditioner = preconditioner;
+  S.ub_grad = grad;
+  ev->spse.blocks_ready = false;  // cse_schur_power_series builds its own after IDENTITY / SCHUR_JACOBI
   // Point order: M_p, u_b = b_b - E_b M_p E_b^T b (and the gradient's e
   // rows); then camera order: rhs = F^T u, the gradient's f rows -F^T b and
   // the preconditioner's F^T Q F, each F cell read once.  The status word
@@ -383,7 +385,8 @@ int SchurInit(cse_evaluator* ev, const double* d_jacobian_values, const double* 
     LaunchSchurPass<cse::kSchurInit>(a, s);
   CSE_HIP(hipGetLastError());
   const Group::GradPlan& P = G.grad[0];
-  const int diag = preconditioner == CSE_SCHUR_IDENTITY ? 0 : preconditioner == CSE_SCHUR_JACOBI ? 1 : 2;
+  // POWER_SERIES_EXPANSION is JACOBI's init: the series' blocks are (F^T F + D_f^2)^-1.
+  const int diag = preconditioner == CSE_SCHUR_IDENTITY ? 0 : preconditioner == CSE_SCHUR_SCHUR_JACOBI ? 2 : 1;
   const int parts = (diag ? cse::SymCount<9>() : 0) + 9 * (grad ? 2 : 1);
   if ((rc = S.partial.ensure((size_t)std::max<int64_t>(1, P.nchunks) * parts))) return rc;
   if (diag && (rc = S.precond.ensure((size_t)81 * (S.held ? S.num_active : P.count)))) return rc;
@@ -410,6 +413,131 @@ int SchurInit(cse_evaluator* ev, const double* d_jacobian_values, const double* 
   S.ready = true;
   return CSE_OK;
 }
+
+// ---------------------------------------------------------------------------
+// SCHUR_POWER_SERIES_EXPANSION (spse_kernels.hpp; the kSchurSeries point pass
+// of schur_kernels.hpp)
+// ---------------------------------------------------------------------------
+// The inverse blocks' entries of an f vector (cse_schur_precondition): the
+// cameras' f rows start at f index f_col_base + 9 lo; with held cameras the
+// blocks are the active cameras', from f index 0.
+void SchurBlockRange(const cse_evaluator* ev, int64_t* off, int64_t* n) {
+  const auto& S = ev->schur;
+  const Group::GradPlan& P = ev->groups[0].grad[0];
+  *off = S.held ? 0 : S.f_col_base + 9LL * P.lo;
+  *n = S.held ? S.f_cols : 9LL * P.count;
+}
+
+bool SchurInitBuiltFtfBlocks(const cse_evaluator* ev) {
+  const int pc = ev->schur.preconditioner;
+  return pc == CSE_SCHUR_JACOBI || pc == CSE_SCHUR_POWER_SERIES_EXPANSION;
+}
+
+// The series' scratch, and -- after an init that built no (F^T F + D_f^2)^-1
+// blocks -- blocks of its own, by the pass a JACOBI init runs
+// (SchurCameraPassKernel<9, 1>, SchurCameraFinishKernel) over the u_b records
+// the init left in S.ub: the same kernels on the same inputs, so the blocks
+// are a JACOBI init's bit for bit.  The rhs (and gradient) rows that pass
+// writes go to scratch.
+int SpseEnsure(cse_evaluator* ev) {
+  auto& S = ev->schur;
+  auto& Z = ev->spse;
+  const int64_t n = S.f_cols;
+  int rc;
+  if ((rc = Z.vectors.ensure((size_t)2 * (size_t)std::max<int64_t>(n, 1)))) return rc;
+  if ((rc = Z.state.ensure(1))) return rc;
+  if (!Z.state_host) CSE_HIP(hipHostMalloc((void**)&Z.state_host, sizeof(cse::SpseState)));
+  if (SchurInitBuiltFtfBlocks(ev) || Z.blocks_ready) return CSE_OK;
+  Group& G = ev->groups[0];
+  const Group::GradPlan& P = G.grad[0];
+  const bool grad = S.ub_grad;
+  const int64_t blocks = S.held ? S.num_active : P.count;
+  const int parts = cse::SymCount<9>() + 9 * (grad ? 2 : 1);
+  if ((rc = Z.partial.ensure((size_t)std::max<int64_t>(1, P.nchunks) * parts))) return rc;
+  if ((rc = Z.blocks.ensure((size_t)81 * (size_t)std::max<int64_t>(blocks, 1)))) return rc;
+  if ((rc = Z.rows.ensure((size_t)18 * (size_t)std::max<int64_t>(blocks, 1)))) return rc;
+  cse::SchurArgs a = MakeSchurArgs(ev, nullptr, nullptr);
+  a.ub = S.ub.p;
+  const cse::GradChunks ch{P.chunk_begin.p, P.chunk_off.p, Z.partial.p, P.nchunks};
+  const int64_t d_off = S.held ? S.e_cols : S.e_cols + S.f_col_base + 9LL * P.lo;  // as SchurInit
+  const SchurCameraLaunch L{a,
+                            &P,
+                            ch,
+                            S.D,
+                            d_off,
+                            Z.blocks.p,
+                            ev->status.p + 1,
+                            Z.rows.p,
+                            grad ? Z.rows.p + 9 * blocks : nullptr,
+                            S.held ? S.fcell.p : nullptr,
+                            S.held ? S.cam_rank.p : nullptr};
+  if (grad)
+    LaunchSchurCameraPass<1, true>(L, ev->stream);
+  else
+    LaunchSchurCameraPass<1, false>(L, ev->stream);
+  CSE_HIP(hipGetLastError());
+  Z.blocks_ready = true;
+  return CSE_OK;
+}
+
+// Enqueues the whole series on the evaluator's stream, no host wait:
+// y = (accumulate: y +) sum_{i <= m} (P^-1 Q)^i P^-1 x, m the number of terms
+// the state's stop test admits (power_series_expansion_preconditioner.cc:51-72).
+// SpseEnsure has run.  Writes the series' own scratch, the contribution
+// records and y alone.
+int SpseEnqueue(cse_evaluator* ev, int32_t max_num_iterations, double tolerance, const double* x, double* y,
+                bool accumulate) {
+  const auto& S = ev->schur;
+  auto& Z = ev->spse;
+  hipStream_t s = ev->stream;
+  const int64_t n = S.f_cols;
+  cse::SpseArgs a{};
+  a.n = n;
+  a.blocks = SchurInitBuiltFtfBlocks(ev) ? S.precond.p : Z.blocks.p;
+  SchurBlockRange(ev, &a.pre_off, &a.pre_n);
+  if (a.pre_off < 0 || a.pre_off + a.pre_n > n)
+    return Fail(CSE_ERR_INVALID, "cse_schur_power_series: the inverse blocks do not fit the f columns");
+  a.x = x;
+  a.y = y;
+  a.prev = Z.vectors.p;
+  double* t = Z.vectors.p + std::max<int64_t>(n, 1);
+  a.t = t;
+  a.state = Z.state.p;
+  a.max_num_iterations = max_num_iterations;
+  a.tolerance = tolerance;
+  cse::LaunchSpseZero(a, accumulate, s);
+  const cse::SchurArgs pass = MakeSchurArgs(ev, a.prev, nullptr);
+  const cse::SchurHeldArgs held = MakeSchurHeldArgs(ev);
+  for (int32_t i = 1; i <= max_num_iterations; ++i) {
+    // t = Q prev: the point pass, then the per-camera sums into a zeroed t.
+    if (S.held)
+      LaunchSchurPass<cse::kSchurSeries, false, true>(pass, s, held);
+    else
+      LaunchSchurPass<cse::kSchurSeries>(pass, s);
+    if (n > 0) CSE_HIP(hipMemsetAsync(t, 0, n * sizeof(double), s));
+    int rc = SchurFTail(ev, t, s);
+    if (rc) return rc;
+    cse::LaunchSpseTerm(a, s);
+  }
+  CSE_HIP(hipGetLastError());
+  return CSE_OK;
+}
+
+// cse_schur_solve under a POWER_SERIES init: SchurCgLaunch with the direction
+// step in two parts, z = series(r) enqueued, then the step that takes z as
+// given.  The series' enqueue can only fail in a launch, which CgSolve's
+// hipGetLastError after the iteration reports.
+struct SchurSpseCgLaunch {
+  cse::CgArgs a;
+  cse_evaluator* ev;
+  void Init(bool zero_guess, hipStream_t s) const { cse::LaunchCgInit(a, zero_guess, s); }
+  void InitialResidual(hipStream_t s) const { cse::LaunchCgInitialResidual(a, s); }
+  void Direction(hipStream_t s) const {
+    (void)SpseEnqueue(ev, ev->schur.spse_iterations, 0.0, a.r, a.z, false);
+    cse::LaunchCgDirectionGiven(a, s);
+  }
+  void Update(cse::CgUpdateMode mode, hipStream_t s) const { cse::LaunchCgUpdate(mode, a, s); }
+};
 
 // The pair plan of the explicit complement, from the group's ids as they were
 // uploaded (the descriptor is gone after cse_create).
@@ -933,6 +1061,14 @@ int cse_schur_precondition(cse_evaluator* ev, const double* d_x, double* d_y) {
     CSE_HIP(hipGetLastError());
     return CSE_OK;
   }
+  if (S.preconditioner == CSE_SCHUR_POWER_SERIES_EXPANSION) {
+    // y += series(x), all spse_iterations terms (tolerance 0:
+    // iterative_schur_complement_solver.cc:186-189).
+    if (d_x < d_y + S.f_cols && d_y < d_x + S.f_cols)
+      return Fail(CSE_ERR_INVALID, "cse_schur_precondition: x and y overlap (POWER_SERIES_EXPANSION)");
+    if ((rc = SpseEnsure(ev))) return rc;
+    return SpseEnqueue(ev, S.spse_iterations, 0.0, d_x, d_y, true);
+  }
   const Group::GradPlan& P = ev->groups[0].grad[0];
   // The cameras' f rows start at f index f_col_base + 9 lo; with held
   // cameras the blocks are the active cameras', from f index 0.
@@ -940,6 +1076,44 @@ int cse_schur_precondition(cse_evaluator* ev, const double* d_x, double* d_y) {
   hipLaunchKernelGGL((cse::SchurPrecondApplyKernel<9>), dim3(grid), dim3(cse::kBlockThreads), 0, s,
                      S.precond.p, d_x + off, d_y + off, S.held ? S.f_cols : 9LL * P.count);
   CSE_HIP(hipGetLastError());
+  return CSE_OK;
+}
+
+int cse_schur_set_spse_iterations(cse_evaluator* ev, int32_t max_num_iterations) {
+  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
+  CSE_SINGLE_DEVICE(ev, "cse_schur_set_spse_iterations");
+  if (max_num_iterations < 1)
+    return Fail(CSE_ERR_INVALID, "cse_schur_set_spse_iterations: max_num_iterations is below 1");
+  ev->schur.spse_iterations = max_num_iterations;
+  return CSE_OK;
+}
+
+int cse_schur_power_series(cse_evaluator* ev, int32_t max_num_iterations, double tolerance, const double* d_x,
+                           double* d_y, cse_spse_summary* summary) {
+  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
+  CSE_SINGLE_DEVICE(ev, "cse_schur_power_series");
+  if (!d_x || !d_y) return Fail(CSE_ERR_INVALID, "cse_schur_power_series: null d_x or d_y");
+  if (max_num_iterations < 1)
+    return Fail(CSE_ERR_INVALID, "cse_schur_power_series: max_num_iterations is below 1");
+  // solver.cc:277-281; spelled with the bits, this unit is built with -ffinite-math-only.
+  const uint64_t tol_bits = __builtin_bit_cast(uint64_t, tolerance);
+  const bool negative = (tol_bits >> 63) != 0 && (tol_bits << 1) != 0;  // -0.0 is 0
+  if (negative || ((tol_bits >> 52) & 0x7ff) == 0x7ff)
+    return Fail(CSE_ERR_INVALID, "cse_schur_power_series: tolerance is negative or not finite");
+  int rc = SchurCheck(ev, true);
+  if (rc) return rc;
+  const int64_t n = ev->schur.f_cols;
+  if (d_x < d_y + n && d_y < d_x + n) return Fail(CSE_ERR_INVALID, "cse_schur_power_series: d_x overlaps d_y");
+  if ((rc = SpseEnsure(ev))) return rc;
+  if ((rc = SpseEnqueue(ev, max_num_iterations, tolerance, d_x, d_y, false))) return rc;
+  if (!summary) return CSE_OK;
+  auto& Z = ev->spse;
+  CSE_HIP(hipMemcpyAsync(Z.state_host, Z.state.p, sizeof(cse::SpseState), hipMemcpyDeviceToHost, ev->stream));
+  CSE_HIP(hipStreamSynchronize(ev->stream));
+  summary->num_terms = Z.state_host->num_terms;
+  summary->reserved = 0;
+  summary->norm_first = Z.state_host->norm_first;
+  summary->norm_last = Z.state_host->norm_last;
   return CSE_OK;
 }
 
@@ -1105,6 +1279,11 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
     return Fail(CSE_ERR_UNSUPPORTED,
                 "cse_schur_solve: d_S_values (the explicit Schur complement) is not available with held "
                 "cameras (constant slot-0 blocks); pass NULL for the implicit operator");
+  const bool series = S.preconditioner == CSE_SCHUR_POWER_SERIES_EXPANSION;
+  if (d_S_values && series)
+    return Fail(CSE_ERR_UNSUPPORTED,
+                "cse_schur_solve: d_S_values (the explicit Schur complement) with a POWER_SERIES_EXPANSION "
+                "init; the explicit complement takes SCHUR_JACOBI alone (solver.cc:262-275)");
   if (d_S_values && !S.sparse.uploaded)
     return Fail(CSE_ERR_INVALID,
                 "cse_schur_solve: d_S_values without the block-sparse structure "
@@ -1121,7 +1300,9 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
   a.r = a.p + n;
   a.z = a.r + n;
   a.tmp = a.z + n;
-  if (S.preconditioner != CSE_SCHUR_IDENTITY) {
+  if (series) {
+    if ((rc = SpseEnsure(ev))) return rc;
+  } else if (S.preconditioner != CSE_SCHUR_IDENTITY) {
     // The cameras' inverse blocks start at f index f_col_base + 9 lo
     // (cse_schur_precondition).
     const Group::GradPlan& P = ev->groups[0].grad[0];
@@ -1134,7 +1315,10 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
   a.state = W.state.p;
   a.params = cse::CgParams{o.min_num_iterations, o.max_num_iterations, o.r_tolerance, o.q_tolerance};
   std::memset(summary, 0, sizeof(*summary));
-  if (d_S_values)
+  if (series)
+    rc = CgSolve("cse_schur_solve", SchurSpseCgLaunch{a, ev}, o, W.state_host, ev->stream,
+                 [&](const double* x, double* y) { return cse_schur_multiply(ev, x, y); }, summary);
+  else if (d_S_values)
     rc = CgSolve("cse_schur_solve", SchurCgLaunch{a}, o, W.state_host, ev->stream,
                  [&](const double* x, double* y) { return cse_schur_explicit_multiply(ev, d_S_values, x, y); },
                  summary);

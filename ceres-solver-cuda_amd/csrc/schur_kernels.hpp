@@ -27,6 +27,9 @@
 //          GradientChunkReduceKernel, as the fused gradient's camera rows
 //     back substitution (BackSubstitute, :216-238):  z_b = b_b - F_b x_c,
 //          y_p = w_p, no f-block sum.
+//     series (the power series expansion's Q x = F^T E M E^T F x):  z_b =
+//          F_b x_c as the multiply, u_b = E_b w_p, summed per f block as the
+//          multiply's (no D_f^2 x term).
 // All sums run in a fixed order: results are bit-identical run to run.
 //
 // linear_operators.hip owns the plain (non-template) kernels here
@@ -39,7 +42,14 @@
 
 namespace cse {
 
-enum SchurMode { kSchurInit = 0, kSchurMultiply = 1, kSchurBack = 2 };
+enum SchurMode { kSchurInit = 0, kSchurMultiply = 1, kSchurBack = 2, kSchurSeries = 3 };
+
+// The modes whose z_b is F_b x_c and whose F_b^T u_b go to the contribution
+// records: the multiply, and the power series' product (u_b = E_b w_p, the
+// projected part alone: F^T E (E^T E + D_e^2)^-1 E^T F x,
+// InversePowerSeriesOperatorRightMultiplyAccumulate without its block apply,
+// implicit_schur_complement.cc:146-174).
+constexpr bool SchurFx(int mode) { return mode == kSchurMultiply || mode == kSchurSeries; }
 
 struct SchurArgs {
   int64_t n;               // residual blocks
@@ -171,8 +181,8 @@ __device__ __forceinline__ void SchurLoadBlock(const SchurArgs& a, int64_t i, in
         f0 += F[k] * xv;
         f1 += F[S0 + k] * xv;
       }
-      z[0] = kMode == kSchurMultiply ? f0 : z[0] - f0;
-      z[1] = kMode == kSchurMultiply ? f1 : z[1] - f1;
+      z[0] = SchurFx(kMode) ? f0 : z[0] - f0;
+      z[1] = SchurFx(kMode) ? f1 : z[1] - f1;
     }
     return;
   }
@@ -185,7 +195,7 @@ __device__ __forceinline__ void SchurLoadBlock(const SchurArgs& a, int64_t i, in
       F[2 * k + 1] = v.y;
     }
   }
-  if constexpr (kMode != kSchurMultiply) {
+  if constexpr (!SchurFx(kMode)) {
     const double2 v = *reinterpret_cast<const double2*>(a.b + a.b_base + 2 * i);
     z[0] = v.x;
     z[1] = v.y;
@@ -199,7 +209,7 @@ __device__ __forceinline__ void SchurLoadBlock(const SchurArgs& a, int64_t i, in
       f0 += F[k] * xv;
       f1 += F[S0 + k] * xv;
     }
-    if constexpr (kMode == kSchurMultiply) {
+    if constexpr (SchurFx(kMode)) {
       z[0] = f0;
       z[1] = f1;
     } else {
@@ -222,13 +232,20 @@ __device__ __forceinline__ void SchurEProducts(const double* E, const double* z,
   A[5] = E[2] * E[2] + E[5] * E[5];
 }
 
-// u_b = z_b - E_b w, then F_b^T u_b (S0 values, padded to S0p) to contrib.
-template <int S0>
+// u_b = z_b - E_b w (kSeries: E_b w), then F_b^T u_b (S0 values, padded to
+// S0p) to contrib.
+template <int S0, bool kSeries = false>
 __device__ __forceinline__ void SchurContrib(const SchurArgs& a, int64_t i, const double* F,
                                              const double* E, const double* z, const double* w) {
   constexpr int S0p = (S0 + 1) & ~1;
-  const double u0 = z[0] - (E[0] * w[0] + E[1] * w[1] + E[2] * w[2]);
-  const double u1 = z[1] - (E[3] * w[0] + E[4] * w[1] + E[5] * w[2]);
+  double u0, u1;
+  if constexpr (kSeries) {
+    u0 = E[0] * w[0] + E[1] * w[1] + E[2] * w[2];
+    u1 = E[3] * w[0] + E[4] * w[1] + E[5] * w[2];
+  } else {
+    u0 = z[0] - (E[0] * w[0] + E[1] * w[1] + E[2] * w[2]);
+    u1 = z[1] - (E[3] * w[0] + E[4] * w[1] + E[5] * w[2]);
+  }
   double2* dst = reinterpret_cast<double2*>(a.contrib + (int64_t)S0p * i);
 #pragma unroll
   for (int k = 0; k < S0p / 2; ++k) {
@@ -324,7 +341,7 @@ __global__ __launch_bounds__(kWPB * kWave) void SchurChunkKernel(const SchurArgs
   const long long idw = reinterpret_cast<const long long*>(a.ids)[i];
   const int id0 = (int)idw, id1 = (int)(idw >> 32);
   double z[2] = {0.0, 0.0};
-  if constexpr (kMode != kSchurMultiply) {
+  if constexpr (!SchurFx(kMode)) {
     const double2 v = *reinterpret_cast<const double2*>(a.b + a.b_base + 2 * i);
     z[0] = v.x;
     z[1] = v.y;
@@ -366,8 +383,8 @@ __global__ __launch_bounds__(kWPB * kWave) void SchurChunkKernel(const SchurArgs
       f0 += F[k] * xc[k];
       f1 += F[S0 + k] * xc[k];
     }
-    z[0] = kMode == kSchurMultiply ? f0 : z[0] - f0;
-    z[1] = kMode == kSchurMultiply ? f1 : z[1] - f1;
+    z[0] = SchurFx(kMode) ? f0 : z[0] - f0;
+    z[1] = SchurFx(kMode) ? f1 : z[1] - f1;
   }
   double s[3], A[6];
   SchurEProducts(E, z, s, A);
@@ -433,8 +450,14 @@ __global__ __launch_bounds__(kWPB * kWave) void SchurChunkKernel(const SchurArgs
     if (active) SchurStoreU<kGrad>(a, i, E, z, w);
   } else {
     // F_b^T u_b, staged over the consumed image, out as contiguous pieces.
-    const double u0 = z[0] - (E[0] * w[0] + E[1] * w[1] + E[2] * w[2]);
-    const double u1 = z[1] - (E[3] * w[0] + E[4] * w[1] + E[5] * w[2]);
+    double u0, u1;
+    if constexpr (kMode == kSchurSeries) {
+      u0 = E[0] * w[0] + E[1] * w[1] + E[2] * w[2];
+      u1 = E[3] * w[0] + E[4] * w[1] + E[5] * w[2];
+    } else {
+      u0 = z[0] - (E[0] * w[0] + E[1] * w[1] + E[2] * w[2]);
+      u1 = z[1] - (E[3] * w[0] + E[4] * w[1] + E[5] * w[2]);
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -564,7 +587,7 @@ __global__ __launch_bounds__(kBlockThreads) void SchurBigKernel(const SchurArgs 
       if (in) {
         double F[2 * S0], E[6], z[2];
         SchurLoadBlock<S0, kMode, true>(a, i, id0, F, E, z, cell + MaskRank(act), rank);
-        SchurContrib<S0>(a, i, F, E, z, w);  // zeros for a held row, never read
+        SchurContrib<S0, kMode == kSchurSeries>(a, i, F, E, z, w);  // zeros for a held row, never read
       }
       cell += __builtin_popcountll(act);
     }
@@ -573,7 +596,7 @@ __global__ __launch_bounds__(kBlockThreads) void SchurBigKernel(const SchurArgs 
       const int id0 = (int)reinterpret_cast<const long long*>(a.ids)[i];
       double F[2 * S0], E[6], z[2];
       SchurLoadBlock<S0, kMode>(a, i, id0, F, E, z);
-      SchurContrib<S0>(a, i, F, E, z, w);
+      SchurContrib<S0, kMode == kSchurSeries>(a, i, F, E, z, w);
     }
   }
 }

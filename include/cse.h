@@ -497,8 +497,13 @@ int cse_jacobian_scale_columns(cse_evaluator* ev, double* d_jacobian_values,
 enum cse_schur_preconditioner {
   CSE_SCHUR_IDENTITY = 0,     /* IDENTITY: M^-1 = I */
   CSE_SCHUR_JACOBI = 1,       /* JACOBI: block diagonal (F^T F + D_f^2)^-1 */
-  CSE_SCHUR_SCHUR_JACOBI = 2  /* SCHUR_JACOBI: block diagonal of S, inverted
+  CSE_SCHUR_SCHUR_JACOBI = 2, /* SCHUR_JACOBI: block diagonal of S, inverted
                                  (schur_jacobi_preconditioner.cc:89-98) */
+  CSE_SCHUR_POWER_SERIES_EXPANSION = 3 /* SCHUR_POWER_SERIES_EXPANSION: the
+                                 truncated series of cse_schur_power_series with
+                                 cse_schur_set_spse_iterations terms and
+                                 tolerance 0 (power_series_expansion_
+                                 preconditioner.cc); its init is JACOBI's */
 };
 
 /* The column split: num_cols_e (points) and num_cols_f (cameras). */
@@ -534,8 +539,65 @@ int cse_schur_init_gradient(cse_evaluator* ev, const double* d_jacobian_values, 
  * which assigns y); x and y have num_cols_f entries. */
 int cse_schur_multiply(cse_evaluator* ev, const double* d_x, double* d_y);
 
-/* y += M^-1 x for the preconditioner chosen at init. */
+/* y += M^-1 x for the preconditioner chosen at init.  Under
+ * CSE_SCHUR_POWER_SERIES_EXPANSION y += series(x) with the iteration count of
+ * cse_schur_set_spse_iterations and tolerance 0; x and y may not overlap then
+ * (CSE_ERR_INVALID).  Note the difference: this call ACCUMULATES into y,
+ * cse_schur_power_series ASSIGNS y. */
 int cse_schur_precondition(cse_evaluator* ev, const double* d_x, double* d_y);
+
+/* ---- SCHUR_POWER_SERIES_EXPANSION ----------------------------------------
+ * S^-1 = sum_i (P^-1 Q)^i P^-1 with P = blockdiag(F^T F + D_f^2) and
+ * Q = P - S = F^T E (E^T E + D_e^2)^-1 E^T F, truncated: the reference's
+ * preconditioner SCHUR_POWER_SERIES_EXPANSION and its initial guess
+ * Solver::Options::use_spse_initialization (iterative_schur_complement_
+ * solver.cc:108-118, :186-189).  A term is the passes of one S product on the
+ * same cells (InversePowerSeriesOperatorRightMultiplyAccumulate,
+ * implicit_schur_complement.cc:146-174) and a 9x9 block apply. */
+typedef struct cse_spse_summary {
+  int32_t num_terms;      /* series terms added after the zeroth: 1 .. max_num_iterations */
+  int32_t reserved;
+  double  norm_first;     /* |(FtF+D^2)^-1 x|, the threshold's base */
+  double  norm_last;      /* |last term added| */
+} cse_spse_summary;
+
+/* PowerSeriesExpansionPreconditioner::RightMultiplyAndAccumulate (:51-72), which
+ * despite its name ASSIGNS y (it zeroes y first; cse_schur_precondition
+ * accumulates):
+ *   y = P^-1 x;  prev = y;  threshold = tolerance * |y|
+ *   for i = 1, 2, ...:  term = P^-1 Q prev;  y += term;
+ *                       stop if i >= max_num_iterations or |term| < threshold;  prev = term
+ * x and y have num_cols_f entries and may not overlap.  Needs cse_schur_init
+ * with ANY preconditioner, on every program the implicit operators serve (held
+ * cameras included).  After a JACOBI or POWER_SERIES_EXPANSION init the P^-1
+ * blocks are the init's; after IDENTITY or SCHUR_JACOBI the first call that
+ * follows the init builds them into a buffer of its own, by the pass a JACOBI
+ * init runs (the same blocks bit for bit), and cse_schur_precondition keeps
+ * applying the init's preconditioner.  The zeroth term is what
+ * cse_schur_precondition gives under a JACOBI init.
+ * All max_num_iterations terms are enqueued without a host wait; the norms and
+ * the stop test run on the device, and once the series has stopped the terms
+ * enqueued behind it change nothing, so the result is the same bits whether or
+ * not the host looks.  tolerance 0 never stops early.  summary NULL: the call
+ * is asynchronous on the evaluator's stream; else it waits once on that stream
+ * and fills the summary.  Deterministic.
+ * CSE_ERR_INVALID: no cse_schur_init; NULL d_x or d_y; max_num_iterations < 1;
+ * a tolerance that is negative or not finite (solver.cc:277-281); d_x
+ * overlapping d_y.  CSE_ERR_UNSUPPORTED on a cse_create_multi handle.  Two
+ * num_cols_f vectors, the state, a pinned copy of it and (after IDENTITY or
+ * SCHUR_JACOBI) the block buffer are allocated by the first call, kept, and
+ * released by cse_destroy.
+ * use_spse_initialization is this call into d_x (max_num_spse_iterations,
+ * spse_tolerance, rhs) followed by cse_schur_solve without
+ * CSE_CG_ZERO_INITIAL_GUESS. */
+int cse_schur_power_series(cse_evaluator* ev, int32_t max_num_iterations, double tolerance,
+                           const double* d_x, double* d_y, cse_spse_summary* summary /* may be NULL */);
+
+/* max_num_spse_iterations of the POWER_SERIES_EXPANSION preconditioner
+ * (default 5, linear_solver.h:172): what cse_schur_precondition and
+ * cse_schur_solve run under that init.  Kept across inits.  CSE_ERR_INVALID
+ * below 1. */
+int cse_schur_set_spse_iterations(cse_evaluator* ev, int32_t max_num_iterations);
 
 /* ImplicitSchurComplement::BackSubstitute(x, y) (:216-238): y
  * (num_effective_parameters) = [(E^T E + D_e^2)^-1 E^T (b - F x); x]. */
@@ -652,7 +714,10 @@ typedef struct cse_cg_summary {
 void cse_cg_default_options(cse_cg_options* options);
 
 /* Solves S x = rhs by preconditioned conjugate gradients.  Needs
- * cse_schur_init, whose preconditioner it applies (IDENTITY: z = r).
+ * cse_schur_init, whose preconditioner it applies (IDENTITY: z = r;
+ * POWER_SERIES_EXPANSION: each iteration enqueues z = series(r) and a direction
+ * step that takes z as given; d_S_values is refused with CSE_ERR_UNSUPPORTED
+ * then, the reference allows only SCHUR_JACOBI on the explicit complement).
  *   d_S_values  NULL: the implicit operator (cse_schur_multiply); else the
  *               values cse_schur_complement_sparse wrote
  *               (cse_schur_explicit_multiply); the structure must be uploaded
