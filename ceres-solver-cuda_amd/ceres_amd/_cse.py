@@ -61,6 +61,7 @@ SCHUR_IDENTITY = 0
 SCHUR_JACOBI = 1
 SCHUR_SCHUR_JACOBI = 2
 SCHUR_POWER_SERIES_EXPANSION = 3
+SCHUR_MAX_CLUSTER_CAMERAS = 16  # CSE_SCHUR_MAX_CLUSTER_CAMERAS
 
 # cse_cgnr_preconditioner
 CGNR_IDENTITY = 0
@@ -208,6 +209,8 @@ SIGNATURES = {
     "cse_schur_power_series": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                          C.POINTER(cse_spse_summary)]),
     "cse_schur_set_spse_iterations": (C.c_int, [C.c_void_p, C.c_int32]),
+    "cse_schur_set_clusters": (C.c_int, [C.c_void_p, P_i32, C.c_int64, C.c_int32]),
+    "cse_schur_cluster_jacobi": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cse_schur_complement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "cse_schur_complement_plan": (C.c_int, [C.c_void_p, P_i64, P_i64, P_i64]),
     "cse_schur_complement_sparse_structure": (C.c_int, [C.c_void_p, P_i64, P_i64, P_i64, P_i64, P_i32]),

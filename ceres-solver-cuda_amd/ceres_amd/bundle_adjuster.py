@@ -70,11 +70,29 @@ def parse(argv=None):
                          "instead of on the implicit operator.  Not a faster solve on the shapes measured "
                          "(level at 49 cameras, slower beyond): see DESIGN 3.6b")
     ap.add_argument("--preconditioner", default="jacobi",
-                    choices=["identity", "jacobi", "schur_jacobi", "schur_power_series_expansion"],
+                    choices=["identity", "jacobi", "schur_jacobi", "schur_power_series_expansion",
+                             "cluster_jacobi"],
                     help="iterative_schur's preconditioner (bundle_adjuster.cc default: jacobi); "
+                         "cluster_jacobi: the blocks of S over the camera clusters of "
+                         "--visibility_clustering, factored once per linear solve "
+                         "(cse_schur_cluster_jacobi), in the host loop and with --device_pcg; not with "
+                         "--held_cameras; "
                          "schur_power_series_expansion: --max_num_spse_iterations terms of the series "
                          "of S^-1 per application (cse_schur_power_series), in the host loop and with "
                          "--device_pcg; not with --use_explicit_schur_complement, as the reference")
+    ap.add_argument("--visibility_clustering", default="single_linkage", choices=["single_linkage", "blocks"],
+                    help="cluster_jacobi's camera partition.  single_linkage (the reference's): the "
+                         "connected components of the visibility graph's edges with weight "
+                         "|V_i n V_j| / sqrt(|V_i| |V_j|) >= --cluster_min_similarity, a larger cluster "
+                         "cut into runs of --max_cluster_cameras; blocks (not the reference's): "
+                         "consecutive runs of --max_cluster_cameras cameras, for the synthetic shapes, "
+                         "whose uniformly drawn visibility leaves single linkage with singletons.  The "
+                         "reference's canonical_views clustering is not implemented")
+    ap.add_argument("--cluster_min_similarity", type=float, default=0.9,
+                    help="single_linkage's threshold (the reference's 0.9)")
+    ap.add_argument("--max_cluster_cameras", type=int, default=16,
+                    help="cameras in a cluster at most; 16 is also the most the device takes "
+                         "(one cluster is factored in one workgroup's LDS)")
     ap.add_argument("--max_num_spse_iterations", type=int, default=5,
                     help="terms of the power series, for the preconditioner and for "
                          "--use_spse_initialization (bundle_adjuster.cc's flag)")
@@ -142,6 +160,17 @@ def parse(argv=None):
     if args.use_explicit_schur_complement and args.linear_solver != "iterative_schur":
         raise SystemExit("--use_explicit_schur_complement needs --linear_solver iterative_schur, not "
                          f"{args.linear_solver}")
+    if args.preconditioner == "cluster_jacobi":
+        if args.linear_solver != "iterative_schur":
+            raise SystemExit("--preconditioner cluster_jacobi needs --linear_solver iterative_schur, not "
+                             f"{args.linear_solver}")
+        if args.held_cameras:
+            raise SystemExit("--preconditioner cluster_jacobi does not go with --held_cameras (its pair plan "
+                             "addresses F cells by block index, as the explicit Schur complement's)")
+        if not 1 <= args.max_cluster_cameras <= 16:
+            raise SystemExit("--max_cluster_cameras must be in [1, 16]")
+        if not 0.0 <= args.cluster_min_similarity <= 1.0:
+            raise SystemExit("--cluster_min_similarity must be in [0, 1]")
     series_pre = args.preconditioner == "schur_power_series_expansion"
     if (args.use_spse_initialization or series_pre) and args.linear_solver != "iterative_schur":
         raise SystemExit("--use_spse_initialization and --preconditioner schur_power_series_expansion need "
@@ -331,9 +360,25 @@ def solve(args, stats=None):
 
     if args.linear_solver != "cgnr":
         e_cols, f_cols = ev.schur_structure()
+        # cluster_jacobi: the init builds no preconditioner of its own (IDENTITY);
+        # cse_schur_cluster_jacobi installs the cluster blocks after it.
+        cluster_pre = args.preconditioner == "cluster_jacobi"
         pre = {"identity": ca._cse.SCHUR_IDENTITY, "jacobi": ca._cse.SCHUR_JACOBI,
                "schur_jacobi": ca._cse.SCHUR_SCHUR_JACOBI,
-               "schur_power_series_expansion": ca._cse.SCHUR_POWER_SERIES_EXPANSION}[args.preconditioner]
+               "schur_power_series_expansion": ca._cse.SCHUR_POWER_SERIES_EXPANSION,
+               "cluster_jacobi": ca._cse.SCHUR_IDENTITY}[args.preconditioner]
+        if cluster_pre:
+            from ceres_amd import clustering
+            t0 = time.perf_counter()
+            labels = clustering.cluster_cameras(ci, pi, cams.shape[0], args.visibility_clustering,
+                                                args.cluster_min_similarity, args.max_cluster_cameras)
+            ev.schur_set_clusters(labels)
+            timers.add("Visibility clustering", time.perf_counter() - t0)
+            sizes = np.bincount(labels)
+            print(f"cluster_jacobi: {len(sizes)} clusters of {sizes.min()} to {sizes.max()} cameras "
+                  f"({args.visibility_clustering})")
+            if stats is not None:
+                stats["cluster_sizes"] = sizes
         if pre == ca._cse.SCHUR_POWER_SERIES_EXPANSION:
             ev.schur_set_spse_iterations(args.max_num_spse_iterations)
         rhs = torch.empty(f_cols, dtype=f64, device=dev)
@@ -378,6 +423,14 @@ def solve(args, stats=None):
         # use_spse_initialization: the PCG starts from the series' x0.
         cg_options.flags = 0 if args.use_spse_initialization else ca._cse.CG_ZERO_INITIAL_GUESS
 
+    def check_cluster_factor():
+        # A cluster whose factor met a pivot that is not positive was left
+        # adding zeros and raised the status word (the init clears it first);
+        # the next evaluation would overwrite it unread.
+        if cluster_pre and ev.wait() != 0:
+            raise SystemExit("cluster_jacobi: a cluster block of S is not positive definite "
+                             "(cse_schur_cluster_jacobi raised the status word)")
+
     def schur_solve(lam):
         # IterativeSchurComplementSolver (iterative_schur_complement_solver.cc:
         # 63-170): the augmented system [J; sqrt(lam diag(J^T J))] dx = [-r; 0]
@@ -390,6 +443,9 @@ def solve(args, stats=None):
             # SolveReducedLinearSystemUsingConjugateGradients
             # (schur_complement_solver.cc): S once, then the PCG on its blocks.
             ev.schur_complement_sparse_device(S_values.data_ptr())
+        if cluster_pre:
+            # Preconditioner::Update: the cluster blocks of this S, factored.
+            ev.schur_cluster_jacobi_device()
         if args.device_pcg:
             # ConjugateGradientsSolver and BackSubstitute in one call; the zero
             # start as IterativeSchurComplementSolver's.
@@ -402,6 +458,7 @@ def solve(args, stats=None):
                 S_values.data_ptr() if args.use_explicit_schur_complement else None, dx.data_ptr())
             if summary.termination_type == ca._cse.CG_FAILURE:
                 raise SystemExit(f"device PCG failed (reason {summary.reason})")
+            check_cluster_factor()
             return dx, summary.num_iterations
         if args.use_spse_initialization:
             # x0 = the series of S^-1 on rhs (iterative_schur_complement_solver.cc:
@@ -436,6 +493,7 @@ def solve(args, stats=None):
             rz = rz_new
         dx = torch.empty(n, dtype=f64, device=dev)
         ev.schur_back_substitute_device(xf.data_ptr(), dx.data_ptr())
+        check_cluster_factor()
         return dx, it
 
     def dense_schur_solve(lam):

@@ -770,6 +770,24 @@ class Evaluator:
         return _cse.check(_cse.lib().cse_schur_set_spse_iterations(self.handle, int(n)),
                           "cse_schur_set_spse_iterations")
 
+    def schur_set_clusters(self, labels):
+        """The camera partition of CLUSTER_JACOBI: labels[c] in [0, k) for
+        camera c in f-column order, every label used, no cluster above
+        _cse.SCHUR_MAX_CLUSTER_CAMERAS (cse_schur_set_clusters; see
+        ceres_amd.clustering).  Kept across inits."""
+        labels = np.ascontiguousarray(labels, np.int32)
+        k = int(labels.max()) + 1 if labels.size else 0
+        return _cse.check(_cse.lib().cse_schur_set_clusters(
+            self.handle, labels.ctypes.data_as(_cse.P_i32), labels.size, k), "cse_schur_set_clusters")
+
+    def schur_cluster_jacobi_device(self, d_matrices=None):
+        """Forms and factors the cluster blocks of S and makes them the active
+        preconditioner until the next schur_init*_device
+        (cse_schur_cluster_jacobi).  d_matrices: None, or room for the
+        unfactored matrices, sum of (9 |g|)^2 doubles in label order."""
+        return _cse.check(_cse.lib().cse_schur_cluster_jacobi(self.handle, d_matrices),
+                          "cse_schur_cluster_jacobi")
+
     def schur_back_substitute_device(self, d_x, d_y):
         """y = [(E^T E + D_e^2)^-1 E^T (b - F x); x] (BackSubstitute)."""
         return _cse.check(_cse.lib().cse_schur_back_substitute(self.handle, d_x, d_y),

@@ -221,6 +221,25 @@ struct cse_evaluator {
       cse::DevBuf<int32_t> block_col, plan_block, sparse_of_plan, finish, col_block;
       cse::DevBuf<double> contrib;  // [num_blocks][9]: the product's column contributions
     } sparse;
+    // CLUSTER_JACOBI (cse_schur_set_clusters, cse_schur_cluster_jacobi): the
+    // partition as given, the cluster-filtered pair plan with its tile layout
+    // (cse::PlanSchurClusters; built and uploaded when the partition
+    // changes), the unfactored tiles, the factor.  `active` from a
+    // build until the next init: cse_schur_precondition and cse_schur_solve
+    // then apply the factor instead of the init's preconditioner.
+    struct Cluster : cse::SchurClusterCounts {
+      bool set = false, uploaded = false, active = false;
+      std::vector<int32_t> labels;
+      int32_t num_labels = 0;
+      int64_t num_finish = 0, num_plan_blocks = 0, num_plan_chunks = 0;
+      cse::DevBuf<int32_t> block_row, block_col, chunk_block, pairs;
+      cse::DevBuf<int64_t> pair_begin, chunk_off;
+      cse::DevBuf<double> partial;
+      cse::DevBuf<int32_t> tile_of_plan, plan_of_tile, tile_camera, finish;
+      cse::DevBuf<int32_t> camera_begin, cameras;
+      cse::DevBuf<int64_t> first_tile, value_begin;
+      cse::DevBuf<double> tiles, factor, inv_diag;
+    } cluster;
   } schur;
   // cse_schur_solve's scratch (cg_kernels.hpp): the four vectors p, r, z, tmp
   // in one buffer and the state, allocated by the first solve.

@@ -2,7 +2,8 @@
 // solver makes on the evaluator (evaluator.hpp): J x, J^T x and CGNR
 // (operator_kernels.hpp), the column norms and ScaleColumns
 // (column_kernels.hpp), the implicit Schur complement (schur_kernels.hpp),
-// the explicit one (schur_complement_kernels.hpp), cse_schur_solve and CGNR on
+// the explicit one (schur_complement_kernels.hpp), CLUSTER_JACOBI
+// (cluster_kernels.hpp), cse_schur_solve and CGNR on
 // the device (cgnr_kernels.hpp; the vector kernels through cg_kernels.h).  The
 // gradient post-pass kernels are launched through evaluator.hpp's functions:
 // they stay instantiated in cse_evaluator.hip.
@@ -12,6 +13,7 @@
 
 #include "cg_kernels.h"
 #include "cgnr_kernels.hpp"
+#include "cluster_kernels.hpp"
 #include "column_kernels.hpp"
 #include "evaluator.hpp"
 #include "kernel_pickers.hpp"
@@ -368,6 +370,7 @@ int SchurInit(cse_evaluator* ev, const double* d_jacobian_values, const double* 
   S.preconditioner = preconditioner;
   S.ub_grad = grad;
   ev->spse.blocks_ready = false;  // cse_schur_power_series builds its own after IDENTITY / SCHUR_JACOBI
+  S.cluster.active = false;       // the init's own preconditioner is back
   // Point order: M_p, u_b = b_b - E_b M_p E_b^T b (and the gradient's e
   // rows); then camera order: rhs = F^T u, the gradient's f rows -F^T b and
   // the preconditioner's F^T Q F, each F cell read once.  The status word
@@ -677,6 +680,114 @@ cse::SchurPairArgs MakeSchurPairArgs(cse_evaluator* ev) {
   a.partial = Q.partial.p;
   return a;
 }
+
+// ---------------------------------------------------------------------------
+// CLUSTER_JACOBI (cluster_kernels.hpp; cse::PlanSchurClusters)
+// ---------------------------------------------------------------------------
+int SchurClusterCheck(cse_evaluator* ev, const char* what) {
+  if (!ev) return Fail(CSE_ERR_INVALID, "null evaluator");
+  CSE_SINGLE_DEVICE(ev, what);
+  const int rc = SchurCheck(ev, false);
+  if (rc) return rc;
+  if (ev->schur.held)
+    return Fail(CSE_ERR_UNSUPPORTED,
+                std::string(what) + ": CLUSTER_JACOBI is not available with held cameras (constant slot-0 "
+                                    "blocks): the pair plan addresses F cells by block index");
+  return CSE_OK;
+}
+
+// The filtered plan and the tile layout of the partition, built and uploaded
+// once per partition (by cse_schur_set_clusters); every buffer is kept (and
+// grown when a later partition needs more).
+int SchurClusterPlanOf(cse_evaluator* ev) {
+  auto& K = ev->schur.cluster;
+  if (K.uploaded) return CSE_OK;
+  const Group& G = ev->groups[0];
+  std::vector<int32_t> ids;
+  int rc = SchurIds(ev, &ids);
+  if (rc) return rc;
+  const int32_t first_id = (int32_t)(-ev->schur.f_col_base / 9);  // as SchurSparsePlanOf
+  const int64_t C = ev->schur.f_cols / 9;
+  cse::SchurClusterPlan P;
+  if ((rc = cse::PlanSchurClusters(ids.data(), G.n, first_id, C, K.labels.data(), K.num_labels, false, &P)))
+    return rc;
+  hipStream_t s = ev->stream;
+  const cse::SchurPairPlan& Q = P.pairs;
+  rc = K.block_row.upload(Q.block_row.data(), Q.block_row.size(), s);
+  if (!rc) rc = K.block_col.upload(Q.block_col.data(), Q.block_col.size(), s);
+  if (!rc) rc = K.pair_begin.upload(Q.pair_begin.data(), Q.pair_begin.size(), s);
+  if (!rc) rc = K.chunk_off.upload(Q.chunk_off.data(), Q.chunk_off.size(), s);
+  if (!rc) rc = K.chunk_block.upload(Q.chunk_block.data(), Q.chunk_block.size(), s);
+  if (!rc) rc = K.pairs.upload(Q.pairs.data(), Q.pairs.size(), s);
+  if (!rc) rc = K.partial.ensure((size_t)std::max<int64_t>(1, Q.num_chunks * cse::kSchurBlockDoubles));
+  if (!rc) rc = K.tile_of_plan.upload(P.tile_of_plan.data(), P.tile_of_plan.size(), s);
+  if (!rc) rc = K.plan_of_tile.upload(P.plan_of_tile.data(), P.plan_of_tile.size(), s);
+  if (!rc) rc = K.tile_camera.upload(P.tile_camera.data(), P.tile_camera.size(), s);
+  if (!rc) rc = K.finish.upload(P.finish.data(), P.finish.size(), s);
+  if (!rc) rc = K.camera_begin.upload(P.camera_begin.data(), P.camera_begin.size(), s);
+  if (!rc) rc = K.cameras.upload(P.cameras.data(), P.cameras.size(), s);
+  if (!rc) rc = K.first_tile.upload(P.first_tile.data(), P.first_tile.size(), s);
+  if (!rc) rc = K.value_begin.upload(P.value_begin.data(), P.value_begin.size(), s);
+  if (!rc) rc = K.tiles.ensure((size_t)std::max<int64_t>(1, P.num_tiles * cse::kSchurBlockDoubles));
+  if (!rc) rc = K.factor.ensure((size_t)std::max<int64_t>(1, P.num_tiles * cse::kSchurBlockDoubles));
+  if (!rc) rc = K.inv_diag.ensure((size_t)std::max<int64_t>(1, 9 * C));
+  // The copies read P's tables: wait before P goes out of scope.
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = Fail(CSE_ERR_HIP, "cluster plan upload failed");
+  if (rc) return rc;
+  static_cast<cse::SchurClusterCounts&>(K) = P;
+  K.num_finish = (int64_t)P.finish.size();
+  K.num_plan_blocks = Q.num_blocks;
+  K.num_plan_chunks = Q.num_chunks;
+  // One cluster in one workgroup's LDS: above 64 KiB the kernels need the
+  // limit raised.
+  CSE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&cse::ClusterFactorKernel<9>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)cse::ClusterFactorLds(cse::kSchurMaxClusterCameras)));
+  CSE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&cse::ClusterApplyKernel<9>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)cse::ClusterApplyLds(cse::kSchurMaxClusterCameras)));
+  K.uploaded = true;
+  return CSE_OK;
+}
+
+cse::ClusterArgs MakeClusterArgs(cse_evaluator* ev) {
+  const auto& K = ev->schur.cluster;
+  cse::ClusterArgs a{};
+  a.camera_begin = K.camera_begin.p;
+  a.cameras = K.cameras.p;
+  a.first_tile = K.first_tile.p;
+  a.value_begin = K.value_begin.p;
+  a.tiles = K.tiles.p;
+  a.factor = K.factor.p;
+  a.inv_diag = K.inv_diag.p;
+  a.status = ev->status.p + 1;
+  return a;
+}
+
+// y (+)= M^-1 x over every cluster; every f entry belongs to one cluster, so
+// without `accumulate` y is assigned whole.
+void LaunchClusterApply(cse_evaluator* ev, const double* x, double* y, bool accumulate) {
+  const auto& K = ev->schur.cluster;
+  if (K.num_clusters <= 0) return;
+  hipLaunchKernelGGL((cse::ClusterApplyKernel<9>), dim3((unsigned)K.num_clusters), dim3(cse::kClusterThreads),
+                     cse::ClusterApplyLds(K.max_cameras), ev->stream, MakeClusterArgs(ev), x, y,
+                     accumulate ? 1 : 0);
+}
+
+// cse_schur_solve under the cluster preconditioner: as SchurSpseCgLaunch, the
+// direction step in two parts, z = M^-1 r by the apply kernel, then the step
+// that takes z as given.
+struct SchurClusterCgLaunch {
+  cse::CgArgs a;
+  cse_evaluator* ev;
+  void Init(bool zero_guess, hipStream_t s) const { cse::LaunchCgInit(a, zero_guess, s); }
+  void InitialResidual(hipStream_t s) const { cse::LaunchCgInitialResidual(a, s); }
+  void Direction(hipStream_t s) const {
+    LaunchClusterApply(ev, a.r, a.z, false);
+    cse::LaunchCgDirectionGiven(a, s);
+  }
+  void Update(cse::CgUpdateMode mode, hipStream_t s) const { cse::LaunchCgUpdate(mode, a, s); }
+};
 
 // ---------------------------------------------------------------------------
 // cse_schur_solve: the reference's conjugate gradients on the device
@@ -1055,6 +1166,11 @@ int cse_schur_precondition(cse_evaluator* ev, const double* d_x, double* d_y) {
   const auto& S = ev->schur;
   hipStream_t s = ev->stream;
   const unsigned grid = (unsigned)((S.f_cols + cse::kBlockThreads - 1) / cse::kBlockThreads);
+  if (S.cluster.active) {  // CLUSTER_JACOBI: y += M^-1 x by the factor
+    LaunchClusterApply(ev, d_x, d_y, true);
+    CSE_HIP(hipGetLastError());
+    return CSE_OK;
+  }
   if (S.preconditioner == CSE_SCHUR_IDENTITY) {  // IdentityPreconditioner: y += x
     hipLaunchKernelGGL(cse::AxpyKernel, dim3(grid), dim3(cse::kBlockThreads), 0, s, d_x, d_y,
                        S.f_cols);
@@ -1253,6 +1369,87 @@ int cse_schur_explicit_multiply(cse_evaluator* ev, const double* d_values, const
   return CSE_OK;
 }
 
+int cse_schur_set_clusters(cse_evaluator* ev, const int32_t* cluster_of_camera, int64_t num_cameras,
+                           int32_t num_clusters) {
+  int rc = SchurClusterCheck(ev, "cse_schur_set_clusters");
+  if (rc) return rc;
+  auto& K = ev->schur.cluster;
+  if (!cluster_of_camera) return Fail(CSE_ERR_INVALID, "cse_schur_set_clusters: null cluster_of_camera");
+  if (num_cameras != ev->schur.f_cols / 9)
+    return Fail(CSE_ERR_INVALID, "cse_schur_set_clusters: num_cameras is " + std::to_string(num_cameras) +
+                                     ", the program has " + std::to_string(ev->schur.f_cols / 9) +
+                                     " (num_cols_f / 9)");
+  if ((rc = cse::ValidateSchurClusters(cluster_of_camera, num_cameras, num_clusters))) return rc;
+  // The structure is rebuilt only when the partition changes.
+  if (K.set && K.num_labels == num_clusters && (int64_t)K.labels.size() == num_cameras &&
+      std::equal(K.labels.begin(), K.labels.end(), cluster_of_camera))
+    return CSE_OK;
+  try {
+    K.labels.assign(cluster_of_camera, cluster_of_camera + num_cameras);
+  } catch (const std::bad_alloc&) {
+    K.set = false;
+    return Fail(CSE_ERR_OOM, "cse_schur_set_clusters: host allocation failed");
+  }
+  K.num_labels = num_clusters;
+  K.uploaded = false;
+  K.active = false;  // a factor of the earlier partition
+  // The filtered plan and the tile layout now, on the host, so that no linear
+  // solve pays for them.
+  K.set = true;
+  if ((rc = SchurClusterPlanOf(ev))) K.set = false;
+  return rc;
+}
+
+int cse_schur_cluster_jacobi(cse_evaluator* ev, double* d_matrices) {
+  int rc = SchurClusterCheck(ev, "cse_schur_cluster_jacobi");
+  if (rc) return rc;
+  auto& S = ev->schur;
+  auto& K = S.cluster;
+  if (!S.ready) return Fail(CSE_ERR_INVALID, "cse_schur_cluster_jacobi: cse_schur_init has not run");
+  if (!K.set) return Fail(CSE_ERR_INVALID, "cse_schur_cluster_jacobi: cse_schur_set_clusters has not run");
+  if ((rc = SchurClusterPlanOf(ev))) return rc;
+  hipStream_t s = ev->stream;
+  // The cluster's cells by the explicit complement's kernels over the filtered
+  // plan, stored tile by tile; the tiles no block writes are zero.
+  cse::SchurPairArgs a = MakeSchurPairArgs(ev);
+  a.block_row = K.block_row.p;
+  a.block_col = K.block_col.p;
+  a.pair_begin = K.pair_begin.p;
+  a.chunk_off = K.chunk_off.p;
+  a.chunk_block = K.chunk_block.p;
+  a.pairs = K.pairs.p;
+  a.nblocks = K.num_plan_blocks;
+  a.nchunks = K.num_plan_chunks;
+  a.partial = K.partial.p;
+  a.sparse_of_plan = K.tile_of_plan.p;
+  a.plan_block = K.plan_of_tile.p;
+  a.sparse_col = K.tile_camera.p;
+  a.finish = K.finish.p;
+  a.nfinish = K.num_finish;
+  a.values = K.tiles.p;
+  if (K.num_tiles > 0)
+    CSE_HIP(hipMemsetAsync(K.tiles.p, 0, (size_t)K.num_tiles * cse::kSchurBlockDoubles * sizeof(double), s));
+  if (K.num_plan_chunks > 0)
+    hipLaunchKernelGGL((cse::SchurPairChunkKernel<9, true>),
+                       dim3((unsigned)((K.num_plan_chunks + cse::kWavesPerBlock - 1) / cse::kWavesPerBlock)),
+                       dim3(cse::kBlockThreads), 0, s, a);
+  if (K.num_finish > 0) {
+    const int64_t entries = K.num_finish * cse::kSchurBlockDoubles;
+    hipLaunchKernelGGL((cse::SchurSparseFinishKernel<9>),
+                       dim3((unsigned)((entries + cse::kBlockThreads - 1) / cse::kBlockThreads)),
+                       dim3(cse::kBlockThreads), 0, s, a);
+  }
+  if (K.num_clusters > 0) {
+    cse::ClusterArgs c = MakeClusterArgs(ev);
+    c.matrices = d_matrices;
+    hipLaunchKernelGGL((cse::ClusterFactorKernel<9>), dim3((unsigned)K.num_clusters),
+                       dim3(cse::kClusterThreads), cse::ClusterFactorLds(K.max_cameras), s, c);
+  }
+  CSE_HIP(hipGetLastError());
+  K.active = true;
+  return CSE_OK;
+}
+
 void cse_cg_default_options(cse_cg_options* o) {
   if (!o) return;
   std::memset(o, 0, sizeof(*o));
@@ -1279,7 +1476,8 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
     return Fail(CSE_ERR_UNSUPPORTED,
                 "cse_schur_solve: d_S_values (the explicit Schur complement) is not available with held "
                 "cameras (constant slot-0 blocks); pass NULL for the implicit operator");
-  const bool series = S.preconditioner == CSE_SCHUR_POWER_SERIES_EXPANSION;
+  const bool clusters = S.cluster.active;
+  const bool series = !clusters && S.preconditioner == CSE_SCHUR_POWER_SERIES_EXPANSION;
   if (d_S_values && series)
     return Fail(CSE_ERR_UNSUPPORTED,
                 "cse_schur_solve: d_S_values (the explicit Schur complement) with a POWER_SERIES_EXPANSION "
@@ -1302,6 +1500,8 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
   a.tmp = a.z + n;
   if (series) {
     if ((rc = SpseEnsure(ev))) return rc;
+  } else if (clusters) {
+    // z = M^-1 r outside the direction kernel (SchurClusterCgLaunch).
   } else if (S.preconditioner != CSE_SCHUR_IDENTITY) {
     // The cameras' inverse blocks start at f index f_col_base + 9 lo
     // (cse_schur_precondition).
@@ -1317,6 +1517,13 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
   std::memset(summary, 0, sizeof(*summary));
   if (series)
     rc = CgSolve("cse_schur_solve", SchurSpseCgLaunch{a, ev}, o, W.state_host, ev->stream,
+                 [&](const double* x, double* y) { return cse_schur_multiply(ev, x, y); }, summary);
+  else if (clusters && d_S_values)
+    rc = CgSolve("cse_schur_solve", SchurClusterCgLaunch{a, ev}, o, W.state_host, ev->stream,
+                 [&](const double* x, double* y) { return cse_schur_explicit_multiply(ev, d_S_values, x, y); },
+                 summary);
+  else if (clusters)
+    rc = CgSolve("cse_schur_solve", SchurClusterCgLaunch{a, ev}, o, W.state_host, ev->stream,
                  [&](const double* x, double* y) { return cse_schur_multiply(ev, x, y); }, summary);
   else if (d_S_values)
     rc = CgSolve("cse_schur_solve", SchurCgLaunch{a}, o, W.state_host, ev->stream,

@@ -1069,7 +1069,8 @@ int64_t FindCgnrBlock(const CgnrBlockPlan& plan, int64_t delta, const CgnrRun** 
   return it->first_block + k / it->tangent_size;
 }
 
-int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPlan* plan) {
+int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPlan* plan,
+                   const int32_t* cluster, int32_t first_id) {
   *plan = SchurPairPlan{};
   if (n >= ((int64_t)1 << 31))
     return CseFail(CSE_ERR_UNSUPPORTED, "Schur complement plan: 2^31 or more residual blocks");
@@ -1087,6 +1088,8 @@ int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPla
     const int64_t C = (int64_t)cmax - cmin + 1;
     // Pass 1: pairs per block, in a dense C x C table (upper triangle used).
     std::vector<int64_t> at((size_t)(C * C), 0);
+    // The filter: a block is kept when its two cameras carry one label.
+    const int32_t* label = cluster ? cluster + ((int64_t)cmin - first_id) : nullptr;
     auto each_pair = [&](auto&& f) {
       int64_t r0 = 0;
       for (int64_t i = 1; i <= n; ++i) {
@@ -1095,7 +1098,7 @@ int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPla
           const int64_t c = ids[2 * b] - cmin;
           for (int64_t b2 = r0; b2 < i; ++b2) {
             const int64_t c2 = ids[2 * b2] - cmin;
-            if (c <= c2) f(c * C + c2, b, b2);
+            if (c <= c2 && (!label || label[c] == label[c2])) f(c * C + c2, b, b2);
           }
         }
         r0 = i;
@@ -1208,6 +1211,122 @@ int PlanSchurSparse(const int32_t* ids, int64_t n, const SchurPairPlan& plan, in
   } catch (const std::bad_alloc&) {
     *sparse = SchurSparsePlan{};
     return CseFail(CSE_ERR_OOM, "block-sparse Schur complement: host allocation failed");
+  }
+  return CSE_OK;
+}
+
+int ValidateSchurClusters(const int32_t* cluster, int64_t C, int32_t num_clusters) {
+  if (!cluster) return CseFail(CSE_ERR_INVALID, "cluster partition: null cluster_of_camera");
+  if (C < 0 || num_clusters < 0 || (C > 0 && num_clusters < 1) || num_clusters > C)
+    return CseFail(CSE_ERR_INVALID, "cluster partition: num_clusters is not in [1, num_cameras]");
+  try {
+    std::vector<int32_t> size((size_t)num_clusters, 0);
+    for (int64_t c = 0; c < C; ++c) {
+      if (cluster[c] < 0 || cluster[c] >= num_clusters)
+        return CseFail(CSE_ERR_INVALID, "cluster partition: camera " + std::to_string(c) + " has label " +
+                                            std::to_string(cluster[c]) + ", outside [0, " +
+                                            std::to_string(num_clusters) + ")");
+      ++size[(size_t)cluster[c]];
+    }
+    for (int32_t g = 0; g < num_clusters; ++g) {
+      if (size[(size_t)g] == 0)
+        return CseFail(CSE_ERR_INVALID, "cluster partition: label " + std::to_string(g) + " is not used");
+      if (size[(size_t)g] > kSchurMaxClusterCameras)
+        return CseFail(CSE_ERR_UNSUPPORTED, "cluster partition: cluster " + std::to_string(g) + " has " +
+                                                std::to_string(size[(size_t)g]) + " cameras, more than " +
+                                                std::to_string(kSchurMaxClusterCameras) +
+                                                " (one cluster is factored in the LDS of one workgroup)");
+    }
+  } catch (const std::bad_alloc&) {
+    return CseFail(CSE_ERR_OOM, "cluster partition: host allocation failed");
+  }
+  return CSE_OK;
+}
+
+int PlanSchurClusters(const int32_t* ids, int64_t n, int32_t first_id, int64_t C, const int32_t* cluster,
+                      int32_t num_clusters, bool counts_only, SchurClusterPlan* plan) {
+  *plan = SchurClusterPlan{};
+  int rc = ValidateSchurClusters(cluster, C, num_clusters);
+  if (rc) return rc;
+  try {
+    std::vector<bool> seen((size_t)C, false);
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t c = (int64_t)ids[2 * i] - first_id;
+      if (c < 0 || c >= C) return CseFail(CSE_ERR_INVALID, "cluster plan: an f block outside the cameras");
+      seen[(size_t)c] = true;
+    }
+    if ((rc = PlanSchurPairs(ids, n, counts_only, &plan->pairs, cluster, first_id))) return rc;
+    SchurClusterPlan& Z = *plan;
+    Z.num_clusters = num_clusters;
+    Z.num_cameras = C;
+    std::vector<int32_t> size((size_t)num_clusters, 0);
+    int64_t unobserved = 0;
+    for (int64_t c = 0; c < C; ++c) {
+      ++size[(size_t)cluster[c]];
+      if (!seen[(size_t)c]) ++unobserved;
+    }
+    for (int32_t g = 0; g < num_clusters; ++g) {
+      const int64_t ng = size[(size_t)g];
+      Z.num_tiles += ng * (ng + 1) / 2;
+      Z.num_values += 81 * ng * ng;
+      Z.max_cameras = std::max(Z.max_cameras, ng);
+    }
+    if (Z.num_tiles >= ((int64_t)1 << 31))
+      return CseFail(CSE_ERR_UNSUPPORTED, "cluster plan: 2^31 or more tiles");
+    // As PlanSchurSparse: the blocks of several chunks, and the added diagonals.
+    Z.finish_capacity = Z.pairs.num_chunks - Z.pairs.num_blocks + unobserved;
+    if (counts_only) return CSE_OK;
+    Z.camera_begin.assign((size_t)num_clusters + 1, 0);
+    Z.first_tile.assign((size_t)num_clusters + 1, 0);
+    Z.value_begin.assign((size_t)num_clusters + 1, 0);
+    for (int32_t g = 0; g < num_clusters; ++g) {
+      const int64_t ng = size[(size_t)g];
+      Z.camera_begin[(size_t)g + 1] = Z.camera_begin[(size_t)g] + (int32_t)ng;
+      Z.first_tile[(size_t)g + 1] = Z.first_tile[(size_t)g] + ng * (ng + 1) / 2;
+      Z.value_begin[(size_t)g + 1] = Z.value_begin[(size_t)g] + 81 * ng * ng;
+    }
+    // Cameras in ascending order fill their cluster's list; local[c] is the
+    // rank of camera c inside its cluster.
+    Z.cameras.resize((size_t)C);
+    std::vector<int32_t> local((size_t)C), cursor(Z.camera_begin.begin(), Z.camera_begin.end() - 1);
+    for (int64_t c = 0; c < C; ++c) {
+      const int32_t g = cluster[c];
+      local[(size_t)c] = cursor[(size_t)g] - Z.camera_begin[(size_t)g];
+      Z.cameras[(size_t)cursor[(size_t)g]++] = (int32_t)c;
+    }
+    Z.plan_of_tile.assign((size_t)Z.num_tiles, -1);
+    Z.tile_camera.resize((size_t)Z.num_tiles);
+    for (int32_t g = 0; g < num_clusters; ++g)
+      for (int32_t j = 0; j < size[(size_t)g]; ++j)
+        for (int32_t i = 0; i <= j; ++i)
+          Z.tile_camera[(size_t)(Z.first_tile[(size_t)g] + ClusterTile(i, j))] =
+              Z.cameras[(size_t)(Z.camera_begin[(size_t)g] + i)];
+    Z.tile_of_plan.resize((size_t)Z.pairs.num_blocks);
+    for (int64_t k = 0; k < Z.pairs.num_blocks; ++k) {
+      const int64_t c = (int64_t)Z.pairs.block_row[(size_t)k] - first_id;
+      const int64_t c2 = (int64_t)Z.pairs.block_col[(size_t)k] - first_id;
+      const int64_t t = Z.first_tile[(size_t)cluster[c]] + ClusterTile(local[(size_t)c], local[(size_t)c2]);
+      Z.tile_of_plan[(size_t)k] = (int32_t)t;
+      Z.plan_of_tile[(size_t)t] = (int32_t)k;
+    }
+    for (int32_t g = 0; g < num_clusters; ++g)
+      for (int32_t j = 0; j < size[(size_t)g]; ++j)
+        for (int32_t i = 0; i <= j; ++i) {
+          const int64_t t = Z.first_tile[(size_t)g] + ClusterTile(i, j);
+          const int64_t k = Z.plan_of_tile[(size_t)t];
+          if (k < 0) {
+            Z.empty_tiles.push_back((int32_t)t);
+            // A diagonal tile no block writes: the camera has no residual block.
+            if (i == j) Z.finish.push_back((int32_t)t);
+          } else if (Z.pairs.chunk_off[(size_t)k + 1] - Z.pairs.chunk_off[(size_t)k] != 1) {
+            Z.finish.push_back((int32_t)t);
+          }
+        }
+    if ((int64_t)Z.finish.size() > Z.finish_capacity)
+      return CseFail(CSE_ERR_INVALID, "cluster plan: the finish list exceeds its bound");
+  } catch (const std::bad_alloc&) {
+    *plan = SchurClusterPlan{};
+    return CseFail(CSE_ERR_OOM, "cluster plan: host allocation failed");
   }
   return CSE_OK;
 }

@@ -343,7 +343,51 @@ struct SchurPairPlan : SchurPairCounts {
 // part alone.  Needs a host table of 8 C^2 bytes for C = the f-block id range
 // (1/81 of the dense S the plan is for).  CSE_ERR_UNSUPPORTED when n >= 2^31
 // (pair entries are int32), CSE_ERR_OOM when host memory runs out.
-int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPlan* plan);
+// cluster (may be null: every block): cluster[id - first_id] is the label of f
+// block id; only the blocks whose two f blocks carry one label are kept.  A
+// kept block's pairs, their order and its chunk cut are the unfiltered
+// plan's (the same walk with the other blocks' counts left at zero).
+int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPlan* plan,
+                   const int32_t* cluster = nullptr, int32_t first_id = 0);
+
+// ---- CLUSTER_JACOBI (cse_schur_set_clusters, cse_schur_cluster_jacobi): the
+// cluster-filtered pair plan and where its blocks go.  Cluster g of n_g
+// cameras c_0 < c_1 < .. (camera index = f block id - first_id, in f-column
+// order) owns the n_g (n_g + 1) / 2 tiles of its upper triangle from
+// first_tile[g]: tile first_tile[g] + j (j + 1) / 2 + i, i <= j, is S(c_i, c_j),
+// 81 doubles row-major as the block-sparse store writes a block.
+constexpr int kSchurMaxClusterCameras = 16;
+constexpr int64_t ClusterTile(int64_t i, int64_t j) { return j * (j + 1) / 2 + i; }  // i <= j
+
+struct SchurClusterCounts {
+  int64_t num_clusters = 0, num_cameras = 0;
+  int64_t num_tiles = 0;        // sum of n_g (n_g + 1) / 2
+  int64_t num_values = 0;       // sum of (9 n_g)^2: the unfactored matrices
+  int64_t max_cameras = 0;      // largest n_g
+  int64_t finish_capacity = 0;  // bound on the finish list known from the counts
+};
+struct SchurClusterPlan : SchurClusterCounts {
+  SchurPairPlan pairs;                  // the filtered plan
+  std::vector<int32_t> camera_begin;    // [num_clusters + 1] into cameras
+  std::vector<int32_t> cameras;         // [num_cameras]: ascending inside a cluster
+  std::vector<int64_t> first_tile;      // [num_clusters + 1]
+  std::vector<int64_t> value_begin;     // [num_clusters + 1]: offset of M_g in the matrices
+  std::vector<int32_t> tile_of_plan;    // [pairs.num_blocks]: a plan block's tile
+  std::vector<int32_t> plan_of_tile;    // [num_tiles]: the inverse, -1 = no plan block writes it
+  std::vector<int32_t> tile_camera;     // [num_tiles]: camera index of the tile's row block
+  // The tiles the finish kernel writes: several chunks, or the diagonal of a
+  // camera without residual blocks (D^2 or zeros).  The off-diagonal tiles no
+  // plan block writes are not listed: they are zero, and the caller zeroes them.
+  std::vector<int32_t> finish;
+  std::vector<int32_t> empty_tiles;     // every tile with plan_of_tile = -1, diagonal or not
+};
+// cluster[c], c in [0, C): labels in [0, num_clusters), every label used, no
+// cluster above kSchurMaxClusterCameras (CSE_ERR_INVALID / CSE_ERR_UNSUPPORTED
+// otherwise).  counts_only fills the SchurClusterCounts part and the counts
+// of `pairs` alone.
+int ValidateSchurClusters(const int32_t* cluster, int64_t C, int32_t num_clusters);
+int PlanSchurClusters(const int32_t* ids, int64_t n, int32_t first_id, int64_t C, const int32_t* cluster,
+                      int32_t num_clusters, bool counts_only, SchurClusterPlan* plan);
 
 // ---- The block-sparse Schur complement (cse_schur_complement_sparse,
 // cse_schur_explicit_multiply): S's upper triangle as block-compressed rows,

@@ -599,6 +599,58 @@ int cse_schur_power_series(cse_evaluator* ev, int32_t max_num_iterations, double
  * below 1. */
 int cse_schur_set_spse_iterations(cse_evaluator* ev, int32_t max_num_iterations);
 
+/* ---- CLUSTER_JACOBI -------------------------------------------------------
+ * The reference's visibility-based preconditioner CLUSTER_JACOBI
+ * (visibility_based_preconditioner.cc): M = blockdiag(M_g), M_g = S restricted
+ * to the cameras of cluster g, factored M_g = L_g L_g^T and applied by a
+ * forward and a backward substitution (:424-431).  The partition is the
+ * caller's (ceres_amd/clustering.py computes the reference's single-linkage
+ * one).  One cluster is factored in the LDS of one workgroup, which caps a
+ * cluster at CSE_SCHUR_MAX_CLUSTER_CAMERAS cameras (144 columns: one triangle
+ * of 9x9 tiles takes 88,128 B of the 163,840 B a workgroup may declare). */
+#define CSE_SCHUR_MAX_CLUSTER_CAMERAS 16
+
+/* Host pointer.  cluster_of_camera[c] for camera c = 0 .. num_cameras-1 in
+ * f-column order (num_cameras = num_cols_f / 9), labels in [0, num_clusters),
+ * every label used.  Kept across inits; replaces an earlier partition.  When
+ * the partition changed, the call builds the cluster-filtered pair plan on the
+ * host and uploads it (it waits on the evaluator's stream); the same partition
+ * again costs a comparison.  Needs no cse_schur_init.  A CHANGED partition
+ * also deactivates a factor that cse_schur_cluster_jacobi built for the
+ * earlier one: until the next cse_schur_cluster_jacobi,
+ * cse_schur_precondition and cse_schur_solve apply the init's own
+ * preconditioner again.  The same partition again leaves the factor active.
+ * CSE_ERR_INVALID: NULL cluster_of_camera, wrong num_cameras, a label out of
+ * range, an unused label.  CSE_ERR_UNSUPPORTED: a cluster of more than
+ * CSE_SCHUR_MAX_CLUSTER_CAMERAS cameras (the message names the cluster and
+ * its size); a program with held cameras (the pair plan addresses F cells by
+ * block index); a cse_create_multi handle; a program that is not
+ * Schur-eligible. */
+int cse_schur_set_clusters(cse_evaluator* ev, const int32_t* cluster_of_camera,
+                           int64_t num_cameras, int32_t num_clusters);
+
+/* Needs cse_schur_init (any preconditioner) and cse_schur_set_clusters.  Reads
+ * the bound Jacobian, D and the per-point inverses the init left; for every
+ * cluster g with cameras c0 < c1 < ... forms M_g = S[g, g] (each 9x9 cell the
+ * bits of cse_schur_complement's), factors it and makes the result the active
+ * preconditioner: until the next cse_schur_init, cse_schur_precondition
+ * accumulates y += M^-1 x and cse_schur_solve uses the same apply for
+ * z = M^-1 r, on the implicit operator and on d_S_values.  The next
+ * cse_schur_init restores the init's own preconditioner: call this again after
+ * it, once per linear solve, as Preconditioner::Update is.
+ * d_matrices non-NULL: the UNFACTORED matrices are written too, cluster g as
+ * a dense row-major n_g x n_g matrix with both triangles, n_g = 9 |g|, at
+ * offset sum_{h<g} n_h^2, clusters in label order and cameras ascending inside
+ * a cluster.
+ * Asynchronous on the evaluator's stream, deterministic, no atomics.  A pivot
+ * that is not positive leaves that cluster's apply adding zeros and makes the
+ * next cse_wait return CSE_EVALUATION_FAILED (the init's convention).  The
+ * filtered plan, the factors and the partials are allocated by
+ * cse_schur_set_clusters, kept, and released by cse_destroy.
+ * CSE_ERR_INVALID: no init, no partition.  CSE_ERR_UNSUPPORTED as
+ * cse_schur_set_clusters. */
+int cse_schur_cluster_jacobi(cse_evaluator* ev, double* d_matrices /* may be NULL */);
+
 /* ImplicitSchurComplement::BackSubstitute(x, y) (:216-238): y
  * (num_effective_parameters) = [(E^T E + D_e^2)^-1 E^T (b - F x); x]. */
 int cse_schur_back_substitute(cse_evaluator* ev, const double* d_x, double* d_y);

@@ -1,0 +1,602 @@
+"""GPU: CLUSTER_JACOBI on the device -- cse_schur_set_clusters and
+cse_schur_cluster_jacobi: the cluster blocks M_g = S[g, g] of the Schur
+complement, their Cholesky factors, and the factor applied by
+cse_schur_precondition and inside cse_schur_solve.
+
+1. Every 9 x 9 cell of every M_g (d_matrices) is np.array_equal to the same
+   cell of cse_schur_complement's dense S.
+2. The apply against numpy on the downloaded M_g: for M z = r,
+   eta = |M z - r|_inf / (|M|_inf |z|_inf + |r|_inf) <= n gamma_{3n+1}, the
+   normwise backward-error bound of a Cholesky solve (Higham, Accuracy and
+   Stability of Numerical Algorithms, Thm 10.4; tests/test_schur_cluster.py
+   holds the host replay and numpy itself to it).
+3. cse_schur_solve under the cluster preconditioner against
+   tests/cg_reference.py given the dense M^-1, as tests/test_schur_solve_gpu.py
+   holds every preconditioner: termination type, reason and iteration count
+   equal, x within max(10 d_ref, 1e-14) of the np.longdouble x.
+4. A pivot that is not positive: the status word, that cluster adding zeros.
+5. Refusals.  6. Release.  7. bundle_adjuster.
+
+The evaluators here are this module's own: a cluster preconditioner left
+active on one that another module binds would change that module's results.
+
+Worst figures measured: see DESIGN 3.6f.
+"""
+import functools
+import types
+
+import numpy as np
+import pytest
+
+import ceres_amd as ca
+from ceres_amd import _cse, bal, clustering
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+import schur_solve_util as SU  # noqa: E402
+from test_constant_gpu import held  # noqa: E402
+from test_schur_cluster import eta, solve_bound  # noqa: E402
+from test_schur_gpu import runs_problem  # noqa: E402
+from test_schur_solve_gpu import filled, options_of, outcome, to_device  # noqa: E402
+from test_spmv_gpu import dense_jacobian  # noqa: E402
+
+LD = np.longdouble
+NAN = float("nan")
+worst = {"eta": (0.0, None), "pcg": (0.0, None)}
+
+
+def note(kind, value, case):
+    if value > worst[kind][0]:
+        worst[kind] = (value, case)
+    return worst[kind]
+
+
+def partitions(num):
+    """name -> labels.  interleaved: cameras 0, 3, 6, .. / 1, 4, .. / 2, 5, ..
+    (no cluster contiguous); uneven: sizes 1, 2, 3, .. in camera order."""
+    out = {"singletons": np.arange(num), "interleaved": np.arange(num) % 3,
+           "halves": np.arange(num) // ((num + 1) // 2), "blocks16": np.arange(num) // 16,
+           "uneven": clustering.relabel(np.floor(np.sqrt(2 * np.arange(num) + 0.25) - 0.5).astype(int))}
+    if num <= 16:
+        out["one"] = np.zeros(num, int)
+    return {k: v.astype(np.int32) for k, v in out.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def device_problem(which):
+    """One evaluator per problem, kept for this module: its Jacobian, D and b
+    on the device.  c.S (numpy, float64) is computed on first use."""
+    dev = torch.device("cuda", 0)
+    prog = SU.make_program(which)
+    ev = ca.Evaluator(prog, stream=torch.cuda.current_stream(dev).cuda_stream)
+    ok, _, _, _, jv = ev.evaluate()
+    assert ok
+    e_cols, f_cols = ev.schur_structure()
+    c = types.SimpleNamespace(which=which, prog=prog, ev=ev, jv=jv, e_cols=e_cols, f_cols=f_cols,
+                              num_cameras=f_cols // 9)
+    c.J = dense_jacobian(prog, jv) if f_cols <= 1000 else None
+    c.D = SU.damping(c.J, e_cols) if c.J is not None else \
+        np.random.default_rng(1).uniform(0.5, 2.0, prog.num_effective_parameters)
+    c.dj, c.dD, c.db = to_device(jv), to_device(c.D), to_device(SU.right_hand_side(prog))
+    c.rhs = filled(f_cols, NAN)
+    c.values = None
+    return c
+
+
+def init(c, precond=_cse.SCHUR_IDENTITY, dD="own"):
+    dD = c.dD if isinstance(dD, str) else dD
+    c.ev.schur_init_device(c.dj.data_ptr(), None if dD is None else dD.data_ptr(), c.db.data_ptr(),
+                           c.rhs.data_ptr(), precond)
+
+
+def dense_S(c):
+    """cse_schur_complement's S of the current init, NaN pre-filled."""
+    S = torch.full((c.f_cols, c.f_cols), NAN, dtype=torch.float64, device=c.rhs.device)
+    c.ev.schur_complement_device(S.data_ptr())
+    return S.cpu().numpy()
+
+
+def cluster_jacobi(c, labels, want_matrices=True):
+    """Installs the partition and builds; returns [(cameras, M_g)] from
+    d_matrices (NaN pre-filled) and the raw buffer."""
+    labels = np.asarray(labels, np.int32)
+    c.ev.schur_set_clusters(labels)
+    groups = [np.nonzero(labels == g)[0] for g in range(int(labels.max()) + 1)]
+    if not want_matrices:
+        c.ev.schur_cluster_jacobi_device(None)
+        return groups, None
+    total = sum((9 * len(g)) ** 2 for g in groups)
+    buf = filled(total, NAN)
+    c.ev.schur_cluster_jacobi_device(buf.data_ptr())
+    host = buf.cpu().numpy()
+    out, at = [], 0
+    for g in groups:
+        n = 9 * len(g)
+        out.append((g, host[at:at + n * n].reshape(n, n)))
+        at += n * n
+    return out, buf
+
+
+def columns(cams):
+    return (9 * np.asarray(cams)[:, None] + np.arange(9)[None, :]).ravel()
+
+
+def check_cells(matrices, S):
+    for cams, M in matrices:
+        assert not np.isnan(M).any()
+        for a, ca_ in enumerate(cams):
+            for b, cb in enumerate(cams):
+                assert np.array_equal(M[9 * a:9 * a + 9, 9 * b:9 * b + 9],
+                                      S[9 * ca_:9 * ca_ + 9, 9 * cb:9 * cb + 9]), (ca_, cb)
+
+
+# --------------------------------------------------------------------------
+# 1. The cluster matrices.
+# --------------------------------------------------------------------------
+MATRIX_CASES = [("bal", "singletons"), ("bal", "one"), ("bal", "interleaved"), ("bal", "uneven"),
+                ("unobserved", "interleaved"), ("unobserved", "one"), ("unobserved", "singletons"),
+                ("duplicates", "halves"), ("duplicates", "one"),
+                ("runs", "blocks16"), (SU.WIDE, "blocks16"), (SU.WIDE, "interleaved_16")]
+
+
+def labels_of(c, partition):
+    if partition == "interleaved_16":  # ten clusters of 15 cameras, none contiguous
+        return (np.arange(c.num_cameras) % 10).astype(np.int32)
+    return partitions(c.num_cameras)[partition]
+
+
+@pytest.mark.parametrize("which,partition", MATRIX_CASES)
+def test_cluster_matrices_are_the_dense_cells(gpu, which, partition):
+    """Every cell of every M_g has the bits of the dense S's cell.  "bal": 150
+    pairs on a diagonal block and 60 to 90 off it, so blocks of one, two and
+    three chunks; "unobserved": camera 3 shares no point with anyone and has
+    D^2 alone; "duplicates": a point that sees a camera twice; "runs": 140
+    cameras, points of 1 to 130 rows, 9 clusters of up to 16 with most tiles
+    empty; "wide": 150 cameras in clusters of exactly 16 (and one of 6)."""
+    c = device_problem(which)
+    init(c)
+    S = dense_S(c)
+    labels = labels_of(c, partition)
+    matrices, buf = cluster_jacobi(c, labels)
+    assert c.ev.wait() == _cse.CSE_OK
+    check_cells(matrices, S)
+    if which == "unobserved":
+        d2 = c.D[c.e_cols + 27:c.e_cols + 36] ** 2
+        for cams, M in matrices:
+            if 3 in cams:
+                a = list(cams).index(3)
+                assert np.array_equal(M[9 * a:9 * a + 9, 9 * a:9 * a + 9], np.diag(d2))
+                off = np.delete(M[9 * a:9 * a + 9], np.s_[9 * a:9 * a + 9], axis=1)
+                assert off.size == 9 * (len(M) - 9) and not off.any()  # exactly zero
+    # a second call repeats the bits
+    _, again = cluster_jacobi(c, labels)
+    assert torch.equal(buf, again)
+    assert c.ev.wait() == _cse.CSE_OK
+
+
+def test_changed_partition_and_second_init(gpu):
+    """One evaluator through several partitions (the structure is rebuilt) and
+    a second init with another D (the values follow, the structure stays)."""
+    c = device_problem("bal")
+    init(c)
+    S = dense_S(c)
+    for name in ("halves", "singletons", "one", "interleaved", "halves"):
+        matrices, _ = cluster_jacobi(c, partitions(10)[name])
+        check_cells(matrices, S)
+    twice = to_device(2.0 * c.D)  # bound by the init: alive until the next one
+    init(c, _cse.SCHUR_JACOBI, twice)
+    S2 = dense_S(c)
+    assert not np.array_equal(S, S2)
+    matrices, _ = cluster_jacobi(c, partitions(10)["halves"])
+    check_cells(matrices, S2)
+    init(c, _cse.SCHUR_SCHUR_JACOBI, None)  # d_D = NULL: no D^2 on the diagonal
+    S3 = dense_S(c)
+    matrices, _ = cluster_jacobi(c, partitions(10)["interleaved"])
+    check_cells(matrices, S3)
+    assert c.ev.wait() == _cse.CSE_OK
+
+
+# --------------------------------------------------------------------------
+# 2. The apply.
+# --------------------------------------------------------------------------
+def precondition(c, x, y0):
+    dx, dy = to_device(x), to_device(y0)
+    c.ev.schur_precondition_device(dx.data_ptr(), dy.data_ptr())
+    return dy
+
+
+@pytest.mark.parametrize("which,partition", [("bal", "interleaved"), ("bal", "halves"), ("bal", "uneven"),
+                                             ("unobserved", "interleaved"), ("duplicates", "halves"),
+                                             ("runs", "blocks16"), (SU.WIDE, "blocks16"),
+                                             (SU.WIDE, "interleaved_16")])
+def test_apply_solves_every_cluster(gpu, which, partition):
+    c = device_problem(which)
+    init(c)
+    labels = labels_of(c, partition)
+    matrices, _ = cluster_jacobi(c, labels)
+    rng = np.random.default_rng(7)
+    x = rng.normal(size=c.f_cols)
+    z = precondition(c, x, np.zeros(c.f_cols)).cpu().numpy()  # 0 + z: z itself
+    assert c.ev.wait() == _cse.CSE_OK
+    assert np.isfinite(z).all()
+    for cams, M in matrices:
+        cols = columns(cams)
+        e, bound = eta(M, z[cols], x[cols]), solve_bound(len(cols))
+        w = note("eta", e / bound, (which, partition, len(cols)))
+        print(f"{which} {partition} n {len(cols):3d}: eta {e:.3e}, bound {bound:.3e}; "
+              f"worst eta / bound so far {w[0]:.3e} at {w[1]}")
+        assert e <= bound
+    # accumulation into a non-zero y: the same z added, bit for bit; twice the same bits
+    y0 = rng.normal(size=c.f_cols)
+    y = precondition(c, x, y0)
+    assert np.array_equal(y.cpu().numpy(), y0 + z)
+    assert torch.equal(y, precondition(c, x, y0))
+    # x and y may be one buffer: a cluster's segment is read before it is written
+    d = to_device(x)
+    c.ev.schur_precondition_device(d.data_ptr(), d.data_ptr())
+    assert np.array_equal(d.cpu().numpy(), x + z)
+    assert c.ev.wait() == _cse.CSE_OK
+
+
+@pytest.mark.parametrize("which", ["bal", "unobserved", "quaternion"])
+def test_singletons_agree_with_schur_jacobi(gpu, which):
+    """SCHUR_JACOBI multiplies by the inverse of S's diagonal block, this
+    solves with its factor: equal to 1e-12 relative in norm, not bitwise.
+    Into y = 0, so that the gap is relative to M^-1 x itself (S's entries are
+    large here, and a y of order one would swallow it)."""
+    c = device_problem(which)
+    x, y0 = np.random.default_rng(8).normal(size=c.f_cols), np.zeros(c.f_cols)
+    init(c, _cse.SCHUR_SCHUR_JACOBI)
+    want = precondition(c, x, y0).cpu().numpy()
+    cluster_jacobi(c, partitions(c.num_cameras)["singletons"], want_matrices=False)
+    got = precondition(c, x, y0).cpu().numpy()
+    assert c.ev.wait() == _cse.CSE_OK
+    gap = np.linalg.norm(got - want) / np.linalg.norm(want)
+    print(f"{which}: |cluster - schur_jacobi| / |.| {gap:.3e}")
+    assert 0 < gap <= 1e-12
+
+
+def test_a_changed_partition_deactivates_the_factor(gpu):
+    """cse.h: a changed partition brings the init's own preconditioner back
+    until the next build; the same partition again leaves the factor active."""
+    c = device_problem("bal")
+    rng = np.random.default_rng(12)
+    x, y0 = rng.normal(size=c.f_cols), rng.normal(size=c.f_cols)
+    init(c, _cse.SCHUR_IDENTITY)
+    cluster_jacobi(c, partitions(10)["halves"], want_matrices=False)
+    with_factor = precondition(c, x, y0).cpu().numpy()
+    assert not np.array_equal(with_factor, y0 + x)
+    c.ev.schur_set_clusters(partitions(10)["halves"])  # unchanged: still active
+    assert np.array_equal(precondition(c, x, y0).cpu().numpy(), with_factor)
+    c.ev.schur_set_clusters(partitions(10)["interleaved"])  # changed: IDENTITY again
+    assert np.array_equal(precondition(c, x, y0).cpu().numpy(), y0 + x)
+    c.ev.schur_cluster_jacobi_device(None)
+    assert not np.array_equal(precondition(c, x, y0).cpu().numpy(), y0 + x)
+    assert c.ev.wait() == _cse.CSE_OK
+
+
+def test_one_cluster_of_all_solves_S(gpu):
+    """One cluster of all 10 cameras: M = S, and z solves S z = r with S the
+    dense complement."""
+    c = device_problem("bal")
+    init(c)
+    S = dense_S(c)
+    cluster_jacobi(c, partitions(10)["one"], want_matrices=False)
+    r = np.random.default_rng(9).normal(size=c.f_cols)
+    z = precondition(c, r, np.zeros(c.f_cols)).cpu().numpy()
+    assert c.ev.wait() == _cse.CSE_OK
+    e = eta(S, z, r)
+    print(f"eta {e:.3e}, bound {solve_bound(90):.3e}")
+    assert e <= solve_bound(90)
+
+
+# --------------------------------------------------------------------------
+# 3. The PCG.
+# --------------------------------------------------------------------------
+def dense_inverse(matrices, f_cols):
+    Minv = np.zeros((f_cols, f_cols))
+    for cams, M in matrices:
+        cols = columns(cams)
+        Minv[np.ix_(cols, cols)] = np.linalg.inv(M)
+    return Minv
+
+
+def solve(c, option_set, explicit, **more):
+    o = SU.OPTION_SETS[option_set]
+    if o.start == "random":
+        x = to_device(SU.initial_guess(c.S, c.rhs_host))
+        flags = 0
+    else:
+        x = filled(c.f_cols, NAN)
+        flags = _cse.CG_ZERO_INITIAL_GUESS
+    summary = c.ev.schur_solve_device(c.rhs.data_ptr(), x.data_ptr(), options_of(o.options, flags=flags, **more),
+                                      c.values.data_ptr() if explicit else None)
+    return summary, x.cpu().numpy()
+
+
+@pytest.mark.parametrize("explicit", [False, True], ids=["implicit", "explicit"])
+@pytest.mark.parametrize("which,partition", [("bal", "interleaved"), ("bal", "halves"), ("unobserved", "interleaved"),
+                                             ("duplicates", "halves")])
+def test_pcg_parity_with_cg_reference(gpu, which, partition, explicit):
+    c = device_problem(which)
+    if c.values is None:
+        _, block_col, _ = c.ev.schur_complement_sparse_structure()
+        c.values = filled(81 * len(block_col), NAN)
+    init(c)
+    c.ev.schur_complement_sparse_device(c.values.data_ptr())
+    c.S = dense_S(c)
+    c.rhs_host = c.rhs.cpu().numpy()
+    matrices, _ = cluster_jacobi(c, labels_of(c, partition))
+    Minv = dense_inverse(matrices, c.f_cols)
+    for option_set in ("lm", "max4", "min6", "guess", "zero"):
+        ref = SU.reference(c.S, Minv, c.rhs_host, option_set)
+        assert SU.same_outcome(ref.f64, ref.ld)  # a fair input
+        summary, x = solve(c, option_set, explicit)
+        err = float(np.linalg.norm((x.astype(LD) - ref.ld.x).astype(np.float64)) /
+                    np.linalg.norm(ref.ld.x.astype(np.float64)))
+        ratio = err / ref.d_ref if ref.d_ref > 0 else 0.0
+        w = note("pcg", ratio, (which, partition, option_set, explicit))
+        print(f"{which} {partition} {option_set}: {outcome(summary)} reference {ref.ld[1:4]} error {err:.3e} "
+              f"d_ref {ref.d_ref:.3e} ratio {ratio:.2f}; worst so far {w[0]:.2f} at {w[1]}")
+        assert outcome(summary) == (ref.ld.termination_type, ref.ld.reason, ref.ld.num_iterations)
+        assert np.isfinite(x).all()
+        assert err <= max(10 * ref.d_ref, 1e-14)
+        # check_period 4 and a repeat: the bits do not depend on it
+        for period in (4, 1):
+            s2, x2 = solve(c, option_set, explicit, check_period=period)
+            assert np.array_equal(x2, x) and outcome(s2) == outcome(summary), period
+            assert (s2.norm_r, s2.rho, s2.pq) == (summary.norm_r, summary.rho, summary.pq)
+    assert c.ev.wait() == _cse.CSE_OK
+    # the next init brings its own preconditioner back
+    rng = np.random.default_rng(10)
+    xx, y0 = rng.normal(size=c.f_cols), rng.normal(size=c.f_cols)
+    init(c, _cse.SCHUR_IDENTITY)
+    assert np.array_equal(precondition(c, xx, y0).cpu().numpy(), y0 + xx)
+    back = _cse.SCHUR_JACOBI if which == "duplicates" else _cse.SCHUR_SCHUR_JACOBI  # refused with duplicates
+    init(c, back)
+    got = precondition(c, xx, y0).cpu().numpy()
+    want = y0 + SU.dense_preconditioner(back, c.S, c.J, c.e_cols, c.D) @ xx
+    assert np.linalg.norm(got - want) <= 1e-11 * np.linalg.norm(want)
+    s_jacobi, _ = solve(c, "zero", explicit)
+    cluster_jacobi(c, partitions(c.num_cameras)["one"], want_matrices=False)
+    s_one, _ = solve(c, "zero", explicit)
+    print(f"iterations: the init's own {s_jacobi.num_iterations}, one cluster (M = S) {s_one.num_iterations}")
+    assert s_one.num_iterations <= 2 < s_jacobi.num_iterations
+
+
+@pytest.mark.parametrize("explicit", [False, True], ids=["implicit", "explicit"])
+def test_solve_and_back_substitution_match_dense_normal_equations(gpu, explicit):
+    """tests/test_schur_solve_gpu.py's test of the same name under the cluster
+    preconditioner: runs_problem(seed=8), 140 cameras in blocks of 16, to 1e-8
+    of the dense normal equations' solution."""
+    prog = runs_problem(seed=8)
+    dev = torch.device("cuda", 0)
+    ev = ca.Evaluator(prog, stream=torch.cuda.current_stream(dev).cuda_stream)
+    ok, cost, r, g, jv = ev.evaluate()
+    J = dense_jacobian(prog, jv)
+    n = prog.num_effective_parameters
+    e_cols, f_cols = ev.schur_structure()
+    D = np.sqrt(1e-2 * np.maximum(np.sum(J * J, axis=0), 1e-6))
+    b = -r
+    dj, dD, db = to_device(jv), to_device(D), to_device(b)
+    rhs = filled(f_cols, NAN)
+    ev.schur_init_device(dj.data_ptr(), dD.data_ptr(), db.data_ptr(), rhs.data_ptr(), _cse.SCHUR_IDENTITY)
+    values = None
+    if explicit:
+        _, block_col, _ = ev.schur_complement_sparse_structure()
+        values = filled(81 * len(block_col), NAN)
+        ev.schur_complement_sparse_device(values.data_ptr())
+    ev.schur_set_clusters(clustering.blocks(f_cols // 9, 16))
+    ev.schur_cluster_jacobi_device()
+    xf, step = filled(f_cols, NAN), filled(n, NAN)
+    o = _cse.cg_options(max_num_iterations=2000, r_tolerance=1e-12, q_tolerance=-1.0,
+                        flags=_cse.CG_ZERO_INITIAL_GUESS, check_period=8)
+    s = ev.schur_solve_device(rhs.data_ptr(), xf.data_ptr(), o, None if values is None else values.data_ptr(),
+                              step.data_ptr())
+    assert ev.wait() == _cse.CSE_OK
+    print(outcome(s), s.norm_r / s.norm_rhs)
+    assert (s.termination_type, s.reason) == (_cse.CG_SUCCESS, _cse.CG_REASON_R_TOLERANCE)
+    ref = np.linalg.solve(J.T @ J + np.diag(D * D), J.T @ b)
+    got = step.cpu().numpy()
+    assert np.array_equal(got[e_cols:], xf.cpu().numpy())
+    assert np.linalg.norm(got - ref) <= 1e-8 * np.linalg.norm(ref)
+    ev.close()
+
+
+# --------------------------------------------------------------------------
+# 4. Status.
+# --------------------------------------------------------------------------
+def test_a_failed_pivot_raises_the_status_word(gpu):
+    """d_D = NULL: the unobserved camera 3 has a zero diagonal block, and the
+    cluster that holds it fails its first pivot there.  cse_wait reports it,
+    that cluster's segment of y is unchanged, the other clusters are right;
+    with D > 0 the same call is clean."""
+    c = device_problem("unobserved")
+    labels = np.array([0, 1, 1, 0, 2, 2, 0, 1], np.int32)  # camera 3 with 0 and 6
+    init(c, _cse.SCHUR_IDENTITY, None)
+    assert c.ev.wait() == _cse.CSE_OK  # the init itself is clean: every point has two blocks
+    matrices, _ = cluster_jacobi(c, labels)
+    rng = np.random.default_rng(11)
+    x, y0 = rng.normal(size=c.f_cols), rng.normal(size=c.f_cols)
+    y = precondition(c, x, y0).cpu().numpy()
+    z = precondition(c, x, np.zeros(c.f_cols)).cpu().numpy()
+    assert c.ev.wait() == _cse.CSE_EVALUATION_FAILED
+    for cams, M in matrices:
+        cols = columns(cams)
+        if 3 in cams:
+            assert np.array_equal(y[cols], y0[cols]) and not z[cols].any()
+        else:
+            assert np.array_equal(y[cols], y0[cols] + z[cols])
+            assert eta(M, z[cols], x[cols]) <= solve_bound(len(cols))
+    init(c)
+    cluster_jacobi(c, labels)
+    y = precondition(c, x, y0).cpu().numpy()
+    assert c.ev.wait() == _cse.CSE_OK
+    assert (y != y0).all()
+
+
+# --------------------------------------------------------------------------
+# 5. Refusals.
+# --------------------------------------------------------------------------
+def test_refusals(gpu):
+    dev = torch.device("cuda", 0)
+    L = _cse.lib()
+    prog = bal.synthetic_program((10, 300, 1500), seed=9)
+
+    def set_clusters(ev, labels, num=None, k=None):
+        labels = None if labels is None else np.ascontiguousarray(labels, np.int32)
+        rc = L.cse_schur_set_clusters(
+            ev.handle, None if labels is None else labels.ctypes.data_as(_cse.P_i32),
+            (10 if labels is None else len(labels)) if num is None else num,
+            (int(labels.max()) + 1 if labels is not None else 1) if k is None else k)
+        if rc < 0:
+            assert _cse.last_error(), "a refusal without a message"
+        return rc
+
+    def build(ev):
+        rc = L.cse_schur_cluster_jacobi(ev.handle, None)
+        if rc < 0:
+            assert _cse.last_error(), "a refusal without a message"
+        return rc
+
+    halves = np.arange(10) // 5
+    # a multi-device handle
+    ev = ca.Evaluator(prog, devices=[0, 0])
+    assert set_clusters(ev, halves) == _cse.CSE_ERR_UNSUPPORTED and "cse_create_multi" in _cse.last_error()
+    assert build(ev) == _cse.CSE_ERR_UNSUPPORTED and "cse_create_multi" in _cse.last_error()
+    ev.close()
+    # not Schur-eligible
+    ev = ca.Evaluator(bal.synthetic_program((10, 300, 1500), format=ca.COMPRESSED_ROW, seed=9))
+    assert set_clusters(ev, halves) == _cse.CSE_ERR_UNSUPPORTED
+    assert build(ev) == _cse.CSE_ERR_UNSUPPORTED
+    ev.close()
+    # held cameras
+    ev = ca.Evaluator(held(counts=(16, 700, 2900), const=(0, 3)))
+    assert set_clusters(ev, np.arange(14) // 7) == _cse.CSE_ERR_UNSUPPORTED and "held" in _cse.last_error()
+    assert build(ev) == _cse.CSE_ERR_UNSUPPORTED and "held" in _cse.last_error()
+    ev.close()
+
+    ev = ca.Evaluator(prog, stream=torch.cuda.current_stream(dev).cuda_stream)
+    ok, _, r, _, jv = ev.evaluate()
+    assert ev.schur_structure()[1] == 90
+    # no init (the partition may be set before it)
+    assert set_clusters(ev, halves) == _cse.CSE_OK
+    assert build(ev) == _cse.CSE_ERR_INVALID and "cse_schur_init has not run" in _cse.last_error()
+    ev.close()
+    ev = ca.Evaluator(prog, stream=torch.cuda.current_stream(dev).cuda_stream)
+    dj, db = to_device(jv), to_device(-r)
+    dD = filled(prog.num_effective_parameters, 1.0)
+    rhs, x, y = filled(90, NAN), filled(90, 1.0), filled(90, 0.0)
+    ev.schur_init_device(dj.data_ptr(), dD.data_ptr(), db.data_ptr(), rhs.data_ptr(), _cse.SCHUR_JACOBI)
+    # no partition
+    assert build(ev) == _cse.CSE_ERR_INVALID and "cse_schur_set_clusters has not run" in _cse.last_error()
+    # the partition's own refusals
+    assert set_clusters(ev, None) == _cse.CSE_ERR_INVALID and "null" in _cse.last_error()
+    for num in (9, 11, 0, 90):
+        assert set_clusters(ev, halves, num=num) == _cse.CSE_ERR_INVALID and "num_cameras" in _cse.last_error()
+    out_of_range = halves.copy()
+    out_of_range[4] = 2
+    assert set_clusters(ev, out_of_range, k=2) == _cse.CSE_ERR_INVALID and "camera 4" in _cse.last_error()
+    negative = halves.copy()
+    negative[7] = -1
+    assert set_clusters(ev, negative, k=2) == _cse.CSE_ERR_INVALID and "camera 7" in _cse.last_error()
+    assert set_clusters(ev, halves, k=3) == _cse.CSE_ERR_INVALID and "label 2 is not used" in _cse.last_error()
+    assert set_clusters(ev, halves, k=0) == _cse.CSE_ERR_INVALID
+    # after the refusals there is still no partition
+    assert build(ev) == _cse.CSE_ERR_INVALID
+    # an unknown preconditioner is still refused by the init
+    assert L.cse_schur_init(ev.handle, dj.data_ptr(), dD.data_ptr(), db.data_ptr(), rhs.data_ptr(), 4) \
+        == _cse.CSE_ERR_INVALID
+    # legal calls afterwards still work
+    assert set_clusters(ev, halves) == _cse.CSE_OK and build(ev) == _cse.CSE_OK
+    ev.schur_precondition_device(x.data_ptr(), y.data_ptr())
+    summary = ev.schur_solve_device(rhs.data_ptr(), x.data_ptr(),
+                                    _cse.cg_options(r_tolerance=1e-8, flags=_cse.CG_ZERO_INITIAL_GUESS))
+    assert ev.wait() == _cse.CSE_OK
+    assert summary.termination_type == _cse.CG_SUCCESS and summary.num_iterations >= 1
+    assert torch.isfinite(y).all() and float(y.norm()) > 0
+    ev.close()
+    # a cluster above the cap: 17 cameras under one label
+    ev = ca.Evaluator(bal.synthetic_program((20, 300, 1500), seed=9))
+    big = (np.arange(20) >= 17).astype(np.int32)
+    assert set_clusters(ev, big) == _cse.CSE_ERR_UNSUPPORTED
+    assert "cluster 0 has 17 cameras" in _cse.last_error()
+    assert set_clusters(ev, (np.arange(20) >= 16).astype(np.int32)) == _cse.CSE_OK  # 16 fit
+    ev.close()
+
+
+# --------------------------------------------------------------------------
+# 6. Release.
+# --------------------------------------------------------------------------
+def test_create_cluster_solve_destroy_does_not_leak(gpu):
+    """The filtered plan, the tiles, the factors and the partials are released
+    by cse_destroy (tests/test_schur_spse_gpu.py's criterion)."""
+    prog = bal.synthetic_program((30, 4000, 16000), loss=ca.Loss.huber(1.0), seed=4)
+    dev = torch.device("cuda", 0)
+    n, m = prog.num_effective_parameters, prog.num_residuals
+    jac = torch.empty(prog.num_jacobian_values, dtype=torch.float64, device=dev)
+    st = torch.from_numpy(prog.state).to(dev)
+    cost = torch.zeros(1, dtype=torch.float64, device=dev)
+    res = torch.empty(m, dtype=torch.float64, device=dev)
+    D = torch.ones(n, dtype=torch.float64, device=dev)
+    rhs, x, y = (torch.zeros(270, dtype=torch.float64, device=dev) for _ in range(3))
+    o = _cse.cg_options(max_num_iterations=20, r_tolerance=1e-6, flags=_cse.CG_ZERO_INITIAL_GUESS)
+
+    def cycle(size):
+        ev = ca.Evaluator(prog, device=0)
+        ev.evaluate_device(st.data_ptr(), cost.data_ptr(), res.data_ptr(), None, jac.data_ptr())
+        ev.schur_init_device(jac.data_ptr(), D.data_ptr(), res.data_ptr(), rhs.data_ptr(), _cse.SCHUR_IDENTITY)
+        ev.schur_set_clusters(clustering.blocks(30, size))
+        ev.schur_cluster_jacobi_device()
+        ev.schur_precondition_device(rhs.data_ptr(), y.data_ptr())
+        ev.schur_solve_device(rhs.data_ptr(), x.data_ptr(), o)
+        ev.schur_set_clusters(clustering.blocks(30, size // 2))  # a second structure on the same handle
+        ev.schur_cluster_jacobi_device()
+        assert ev.wait() == 0
+        ev.close()
+
+    cycle(16)
+    cycle(4)
+    torch.cuda.synchronize()
+    free0, _ = torch.cuda.mem_get_info(dev)
+    for k in range(10):
+        cycle(16 if k % 2 else 4)
+    torch.cuda.synchronize()
+    free1, _ = torch.cuda.mem_get_info(dev)
+    assert free0 - free1 < 2 << 20, (free0, free1)
+
+
+# --------------------------------------------------------------------------
+# 7. The driver.
+# --------------------------------------------------------------------------
+DRIVER = ["--synthetic", "problem-16-22106", "--robustify", "--point_sigma", "0.05", "--num_iterations", "3"]
+CLUSTER = ("--preconditioner", "cluster_jacobi", "--visibility_clustering", "blocks")
+
+
+@functools.lru_cache(maxsize=None)
+def driver_run(*extra):
+    from ceres_amd import bundle_adjuster
+    return bundle_adjuster.main(DRIVER + list(extra))
+
+
+@pytest.mark.parametrize("extra", [(), ("--device_pcg",)], ids=["host-loop", "device-pcg"])
+def test_bundle_adjuster(gpu, capsys, extra):
+    """Clusters of 4 reach the jacobi run's final cost to 1e-6 relative with
+    every step accepted; one cluster of all 16 cameras (M = S) takes fewer PCG
+    iterations in every solve than schur_jacobi."""
+    _, want, rows_jacobi = driver_run()
+    c0, c1, rows = driver_run(*CLUSTER, "--max_cluster_cameras", "4", *extra)
+    _, _, rows_schur_jacobi = driver_run("--preconditioner", "schur_jacobi", *extra)
+    _, c16, rows16 = driver_run(*CLUSTER, "--max_cluster_cameras", "16", *extra)
+    print(capsys.readouterr().out)
+    print(f"{extra}: final cost {c1:.12e}, jacobi's {want:.12e}, relative gap {abs(c1 - want) / want:.3e}; "
+          f"ls_iter {[r[6] for r in rows]} against jacobi's {[r[6] for r in rows_jacobi]}")
+    print(f"one cluster of 16: ls_iter {[r[6] for r in rows16]} against schur_jacobi's "
+          f"{[r[6] for r in rows_schur_jacobi]}; final cost {c16:.12e}")
+    assert c1 < c0 and all(r[6] > 0 for r in rows)
+    assert all(r[7] for r in rows) and len(rows) == 3
+    assert abs(c1 - want) <= 1e-6 * want
+    assert len(rows16) == len(rows_schur_jacobi)
+    assert all(a[6] < b[6] for a, b in zip(rows16, rows_schur_jacobi))
