@@ -14,7 +14,8 @@
 //   Invert    per block: mirror the upper triangle, add D^2 on the diagonal,
 //             Cholesky in place, M = L^-T L^-1 (:208-221, m.llt().solve(I)).
 //
-// linear_operators.hip's alone.
+// linear_operators.hip's alone: it owns the plain (non-template) kernels here
+// (DtDxpyKernel, GramBlockKernel).
 #ifndef CSE_CGNR_KERNELS_HPP_
 #define CSE_CGNR_KERNELS_HPP_
 
@@ -23,9 +24,15 @@
 
 #include "column_kernels.hpp"
 #include "operator_kernels.hpp"
-#include "schur_kernels.hpp"
 
 namespace cse {
+
+// y += D .* D .* x (CudaVector::DtDxpy, cgnr_solver.cc:236): cse_cgnr_multiply's.
+__global__ __launch_bounds__(kBlockThreads) void DtDxpyKernel(const double* D, const double* x,
+                                                              double* y, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x;
+  if (i < n) y[i] += D[i] * D[i] * x[i];
+}
 
 constexpr int GramCount(int s) { return s * (s + 1) / 2; }
 
@@ -225,7 +232,7 @@ __global__ __launch_bounds__(kBlockThreads) void GramBlockKernel(const ColumnBlo
 // m: row-major S x S in global memory whose upper triangle holds G; d: the
 // block's entries of D, or null.  Writes M = (G + diag(d^2))^-1, both
 // triangles, by the Cholesky factor; false (and m = 0) when a pivot is not
-// positive and finite (PivotOk, schur_kernels.hpp).  A holds L below the
+// positive and finite (PivotOk, operator_kernels.hpp).  A holds L below the
 // diagonal, 1 / L_jj on it and L^-1 transposed above it.
 template <int S>
 __device__ __forceinline__ bool InvertSpdBlock(double* m, const double* d) {

@@ -34,7 +34,7 @@
 //       be contiguous.
 // No atomics, no cross-workgroup ordering but the kernel boundaries.
 //
-// linear_operators.hip alone includes this.
+// schur_operators.hip alone includes this.
 #ifndef CSE_CLUSTER_KERNELS_HPP_
 #define CSE_CLUSTER_KERNELS_HPP_
 

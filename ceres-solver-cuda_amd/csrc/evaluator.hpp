@@ -1,7 +1,8 @@
 // evaluator.hpp -- the evaluator's host-side state (struct cse_evaluator and
 // the device buffers of its groups), shared by cse_evaluator.hip (create,
-// upload, evaluation, Plus) and linear_operators.hip (what a linear solver
-// calls).  A HIP host header: it defines no kernel.
+// upload, evaluation, Plus), linear_operators.hip (the Jacobian-level calls of
+// a linear solver) and schur_operators.hip (cse_schur_*).  A HIP host header:
+// it defines no kernel.
 #ifndef CSE_EVALUATOR_HPP_
 #define CSE_EVALUATOR_HPP_
 
@@ -21,8 +22,9 @@ struct CseMulti;  // multi_device.h
 
 namespace cse {
 
-struct GroupArgs;  // kernel_common.hpp
-struct GradArgs;   // operator_kernels.hpp
+struct GroupArgs;      // kernel_common.hpp
+struct GradArgs;       // operator_kernels.hpp
+struct SchurPairArgs;  // schur_complement_kernels.hpp
 
 inline int Fail(int code, const std::string& msg) { return CseFail(code, msg); }
 
@@ -127,6 +129,38 @@ struct Group : cse::GroupPlan {
   DevBuf<int64_t> runs;
 };
 
+// A pair plan (cse::SchurPairPlan) on the device: its six tables and the chunk
+// partials.  One rule for every holder: each buffer is allocated at exactly
+// the plan's size, the partials at num_chunks blocks (what plan_bytes counts),
+// and after a failure the tables are empty: Upload releases what it had
+// allocated, and a caller whose stream synchronize fails calls Release.  The
+// caller synchronizes before the host plan the copies read goes out of scope.
+struct SchurPairTables {
+  int64_t num_blocks = 0, num_chunks = 0;
+  DevBuf<int32_t> block_row, block_col, chunk_block, pairs;
+  DevBuf<int64_t> pair_begin, chunk_off;
+  DevBuf<double> partial;
+  int Upload(const SchurPairPlan& P, hipStream_t s) {
+    int rc = block_row.upload(P.block_row.data(), P.block_row.size(), s);
+    if (!rc) rc = block_col.upload(P.block_col.data(), P.block_col.size(), s);
+    if (!rc) rc = pair_begin.upload(P.pair_begin.data(), P.pair_begin.size(), s);
+    if (!rc) rc = chunk_off.upload(P.chunk_off.data(), P.chunk_off.size(), s);
+    if (!rc) rc = chunk_block.upload(P.chunk_block.data(), P.chunk_block.size(), s);
+    if (!rc) rc = pairs.upload(P.pairs.data(), P.pairs.size(), s);
+    if (!rc) rc = partial.alloc((size_t)(P.num_chunks * kSchurBlockDoubles));
+    if (rc) {
+      Release();
+      return rc;
+    }
+    num_blocks = P.num_blocks;
+    num_chunks = P.num_chunks;
+    return CSE_OK;
+  }
+  void Release() { *this = SchurPairTables{}; }
+  // The table pointers, nblocks, nchunks and partial of a (schur_operators.hip).
+  void Bind(SchurPairArgs* a) const;
+};
+
 // Waves per workgroup of the CGNR and Schur chunk kernels (one chunk per
 // wave either way); one wave per workgroup, as the Jacobian kernels are
 // launched, measured slower: S x 2.363 -> 2.410 ms, CGNR 2.596 -> 2.614 ms
@@ -205,9 +239,7 @@ struct cse_evaluator {
     // cse_schur_complement; structure only, so it outlives every init.
     struct Pairs : cse::SchurPairCounts {
       bool counted = false, uploaded = false;
-      cse::DevBuf<int32_t> block_row, block_col, chunk_block, pairs;
-      cse::DevBuf<int64_t> pair_begin, chunk_off;
-      cse::DevBuf<double> partial;
+      cse::SchurPairTables tables;
     } pairs;
     // The block-sparse complement's structure (cse::PlanSchurSparse), cached
     // the same way; row_begin and block_col stay on the host too, for
@@ -231,10 +263,8 @@ struct cse_evaluator {
       bool set = false, uploaded = false, active = false;
       std::vector<int32_t> labels;
       int32_t num_labels = 0;
-      int64_t num_finish = 0, num_plan_blocks = 0, num_plan_chunks = 0;
-      cse::DevBuf<int32_t> block_row, block_col, chunk_block, pairs;
-      cse::DevBuf<int64_t> pair_begin, chunk_off;
-      cse::DevBuf<double> partial;
+      int64_t num_finish = 0;
+      cse::SchurPairTables tables;  // the filtered plan
       cse::DevBuf<int32_t> tile_of_plan, plan_of_tile, tile_camera, finish;
       cse::DevBuf<int32_t> camera_begin, cameras;
       cse::DevBuf<int64_t> first_tile, value_begin;
@@ -304,6 +334,8 @@ int LaunchContribReduce(const Group::GradPlan& P, const double* gcontrib, const 
 // add the slot-1 boundary entries and the slot-0 contributions, per
 // parameter block in a fixed order, into out (delta offsets).
 int LaunchFusedGradTail(const Group& G, double* out, hipStream_t s);
+// y += x over n > 0 entries (AxpyKernel, schur_operators.hip's: CGNR comes here for it).
+void LaunchAxpy(const double* x, double* y, int64_t n, hipStream_t s);
 
 }  // namespace cse
 

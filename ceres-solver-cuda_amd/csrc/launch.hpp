@@ -1,7 +1,7 @@
 // launch.hpp -- host-side launches of the evaluator kernels for one functor
 // kind, in their shipped settings (grid, workgroup size, tuning struct).
 //
-// Shared by the library (cse_evaluator.hip, linear_operators.hip and the
+// Shared by the library (cse_evaluator.hip, the two operator units and the
 // kernel TUs through kernel_pickers.hpp) and by user functor kinds, whose
 // kernels are instantiated in the user's hipcc TU
 // (include/ceres_amd/autodiff_cuda.h) the way the reference instantiates
@@ -24,6 +24,8 @@
 namespace cse {
 
 inline int64_t Chunks(int64_t n) { return (n + kWave - 1) / kWave; }
+// The grid of n items at `per` to a workgroup.
+inline dim3 Blocks(int64_t n, int64_t per = kBlockThreads) { return dim3((unsigned)((n + per - 1) / per)); }
 
 // The general kernel: one residual block per lane, offsets through the
 // descriptor's tables (EvaluateTableKernel).

@@ -2,14 +2,22 @@
 // gradient post-pass and the fused gradient's tails, and the Jacobian as a
 // linear operator (J x, J^T x, the CGNR normal operator).  Types, device
 // helpers and template kernels only, so any TU may include it; the plain
-// kernels are in evaluation_kernels.hpp (cse_evaluator.hip's) and
-// schur_kernels.hpp (linear_operators.hip's).
+// kernels are in evaluation_kernels.hpp (cse_evaluator.hip's),
+// schur_kernels.hpp (schur_operators.hip's) and cgnr_kernels.hpp
+// (linear_operators.hip's).
 #ifndef CSE_OPERATOR_KERNELS_HPP_
 #define CSE_OPERATOR_KERNELS_HPP_
 
 #include "evaluate_kernel.hpp"
 
 namespace cse {
+
+// A Cholesky pivot that can be factored: positive and finite.  Bit tests:
+// the kernels are compiled with -ffinite-math-only, which folds NaN checks.
+__device__ __forceinline__ bool PivotOk(double p) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, p);
+  return (b >> 63) == 0 && b != 0 && ((b >> 52) & 0x7ff) != 0x7ff;
+}
 
 // ---------------------------------------------------------------------------
 // Gradient g = J^T r as a deterministic post-pass over the outputs just

@@ -34,7 +34,7 @@
 //   SchurExplicitRowKernel + SchurExplicitColumnKernel   y = S x on those
 //       blocks (cse_schur_explicit_multiply).
 //
-// linear_operators.hip owns the plain (non-template) kernel here
+// schur_operators.hip owns the plain (non-template) kernel here
 // (SchurDiagonalFillKernel): no other TU of the library includes this.
 #ifndef CSE_SCHUR_COMPLEMENT_KERNELS_HPP_
 #define CSE_SCHUR_COMPLEMENT_KERNELS_HPP_

@@ -32,9 +32,9 @@
 //          multiply's (no D_f^2 x term).
 // All sums run in a fixed order: results are bit-identical run to run.
 //
-// linear_operators.hip owns the plain (non-template) kernels here
-// (SchurDiagKernel, AxpyKernel and CGNR's DtDxpyKernel): no other TU of the
-// library includes this.
+// schur_operators.hip owns the plain (non-template) kernels here
+// (SchurDiagKernel and AxpyKernel, which cse_cgnr_precondition reaches through
+// evaluator.hpp's LaunchAxpy): no other TU of the library includes this.
 #ifndef CSE_SCHUR_KERNELS_HPP_
 #define CSE_SCHUR_KERNELS_HPP_
 
@@ -89,13 +89,6 @@ struct SchurHeldArgs {
 // Lanes below `lane` set in mask.
 __device__ __forceinline__ int MaskRank(uint64_t mask) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-// A Cholesky pivot that can be factored: positive and finite.  Bit tests:
-// the kernels are compiled with -ffinite-math-only, which folds NaN checks.
-__device__ __forceinline__ bool PivotOk(double p) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, p);
-  return (b >> 63) == 0 && b != 0 && ((b >> 52) & 0x7ff) != 0x7ff;
 }
 
 // Packed upper triangle of a symmetric 3 x 3: (00, 01, 02, 11, 12, 22).
@@ -620,13 +613,6 @@ __global__ __launch_bounds__(kBlockThreads) void SchurDiagKernel(const double* D
 __global__ __launch_bounds__(kBlockThreads) void AxpyKernel(const double* x, double* y, int64_t n) {
   const int64_t k = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x;
   if (k < n) y[k] += x[k];
-}
-
-// y += D .* D .* x (CudaVector::DtDxpy, cgnr_solver.cc:236): cse_cgnr_multiply's.
-__global__ __launch_bounds__(kBlockThreads) void DtDxpyKernel(const double* D, const double* x,
-                                                              double* y, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * kBlockThreads + threadIdx.x;
-  if (i < n) y[i] += D[i] * D[i] * x[i];
 }
 
 // The init's camera-order pass, one wave per block list chunk (the camera

@@ -198,6 +198,41 @@ def test_changed_partition_and_second_init(gpu):
     assert c.ev.wait() == _cse.CSE_OK
 
 
+def sparse_values(c):
+    """cse_schur_complement_sparse's values of the current init, NaN pre-filled."""
+    values = filled(81 * c.ev.schur_complement_sparse_counts()[1], NAN)
+    c.ev.schur_complement_sparse_device(values.data_ptr())
+    return values
+
+
+@pytest.mark.parametrize("which", ["bal", "unobserved"])
+def test_pair_tables_shared_by_three_consumers(gpu, which):
+    """The dense complement, the cluster matrices and the block-sparse values
+    interleaved on one evaluator after one init: the full pair plan and the
+    cluster-filtered one are two instances of one table type behind one launch
+    of the block store, and neither reads the other's tables or partials.
+    Each block-sparse result has the bits of a fresh evaluator's that builds
+    nothing else; each cluster result the dense S's cells.  "unobserved":
+    camera 3 has no pairs, so an added diagonal and a tile the finish alone
+    writes."""
+    one, fresh = device_problem.__wrapped__(which), device_problem.__wrapped__(which)
+    try:
+        init(fresh)
+        want = sparse_values(fresh)
+        assert fresh.ev.wait() == _cse.CSE_OK and not torch.isnan(want).any()
+        init(one)
+        S = dense_S(one)
+        for name in ("interleaved", "halves"):
+            matrices, _ = cluster_jacobi(one, partitions(one.num_cameras)[name])
+            assert one.ev.wait() == _cse.CSE_OK
+            check_cells(matrices, S)
+            assert torch.equal(sparse_values(one), want), name
+            assert one.ev.wait() == _cse.CSE_OK
+    finally:
+        one.ev.close()
+        fresh.ev.close()
+
+
 # --------------------------------------------------------------------------
 # 2. The apply.
 # --------------------------------------------------------------------------

@@ -23,9 +23,13 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, "ceres-solver-cuda_amd")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-signed-zeros", "-ffinite-math-only",
          "-munsafe-fp-atomics", "-w", "--cuda-device-only", "-S"]
-# The library's kernel-bearing TUs (the Makefile's ISA_TUS).
-KERNEL_TUS = ["csrc/cse_evaluator.hip", "csrc/linear_operators.hip", "csrc/jet_kernels.hip",
-              "csrc/per_block_loss_kernels.hip", "csrc/cg_kernels.hip"]
+
+
+def kernel_tus():
+    """The library's kernel-bearing TUs: the Makefile's ISA_TUS."""
+    out = subprocess.run(["make", "-s", "--no-print-directory", "-C", PKG, "print-isa-tus"],
+                         check=True, capture_output=True, text=True).stdout
+    return ["csrc/%s.hip" % tu for tu in out.split()]
 
 
 def flags_of(src):
@@ -55,7 +59,7 @@ def functions(asm):
 
 
 def main():
-    srcs = sys.argv[1:] or KERNEL_TUS
+    srcs = sys.argv[1:] or kernel_tus()
     names = []
     with tempfile.TemporaryDirectory() as td:
         outs = [os.path.join(td, "k%d.s" % i) for i in range(len(srcs))]
@@ -63,9 +67,12 @@ def main():
                                   cwd=PKG) for s, o in zip(srcs, outs)]
         if any(p.wait() for p in procs):
             sys.exit("compile failed")
-        asm = "\n".join(open(o).read() for o in outs)
-    if True:
-        for name, body in functions(asm):
+        asm = [open(o).read() for o in outs]
+    # File by file: the data labels that end a file (__hip_cuid_*, named after
+    # the source's contents) open no function, and must not take the first
+    # kernel of the next file.
+    for text in asm:
+        for name, body in functions(text):
             h = hashlib.sha1("\n".join(body).encode()).hexdigest()[:16]
             names.append((name, h, len(body)))
     mangled = [n for n, _, _ in names]
