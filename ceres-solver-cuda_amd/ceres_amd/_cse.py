@@ -211,6 +211,8 @@ SIGNATURES = {
     "cse_schur_set_spse_iterations": (C.c_int, [C.c_void_p, C.c_int32]),
     "cse_schur_set_clusters": (C.c_int, [C.c_void_p, P_i32, C.c_int64, C.c_int32]),
     "cse_schur_cluster_jacobi": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cse_schur_set_cluster_forest": (C.c_int, [C.c_void_p, P_i32, C.c_int32]),
+    "cse_schur_cluster_tridiagonal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cse_schur_complement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "cse_schur_complement_plan": (C.c_int, [C.c_void_p, P_i64, P_i64, P_i64]),
     "cse_schur_complement_sparse_structure": (C.c_int, [C.c_void_p, P_i64, P_i64, P_i64, P_i64, P_i32]),

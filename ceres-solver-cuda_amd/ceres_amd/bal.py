@@ -8,6 +8,12 @@
   AngleAxisRotatePoint), t = (N(0,1), N(0,1), -10 + N(0,1)),
   f ~ U[400, 1200], l1 ~ N(0, 0.05^2), l2 ~ N(0, 0.01^2); points
   ~ U[-3, 3]^3; obs = projection + N(0, 1) px, 5% outliers U(-50, 50) px.
+* synthetic_banded(C, P, O, window, seed): the same problem with LOCAL
+  visibility: each point's cameras are drawn from a window of `window`
+  consecutive cameras around a uniformly drawn centre (a camera trajectory;
+  the uniform draw above leaves the visibility-based preconditioners nothing
+  to find).  Named "banded-C-P-wW" (4 P observations) or "banded-C-P-O-wW"
+  wherever a synthetic shape is named.
 * read(path): the BAL text format (examples/bal_problem.cc:72-132).
 * program(...): the Ceres Program for bundle_adjuster's Schur setup
   (examples/bundle_adjuster.cu.cc:307-353 BuildProblem + the points-first
@@ -71,10 +77,53 @@ def synthetic(num_cameras, num_points, num_observations, seed=0xCE2E5, outlier_f
     return _synthetic(num_cameras, num_points, num_observations, seed, outlier_fraction)
 
 
-def _synthetic(num_cameras, num_points, num_observations, seed, outlier_fraction):
+def synthetic_banded(num_cameras, num_points, num_observations, window, seed=0xCE2E5, outlier_fraction=0.05):
+    """synthetic()'s cameras, points, geometry, noise and outliers, but each
+    point's distinct cameras come from a window of `window` consecutive
+    cameras: [s, s + window) with s = centre - window // 2 for a centre drawn
+    uniformly over the cameras, clipped to [0, C - window].  Not cached."""
+    return _synthetic(num_cameras, num_points, num_observations, seed, outlier_fraction, window=window)
+
+
+def parse_banded(name):
+    """(C, P, O, window) of "banded-C-P-wW" (O = 4 P) or "banded-C-P-O-wW";
+    None for any other name."""
+    parts = str(name).split("-")
+    if parts[0] != "banded" or len(parts) not in (4, 5) or not parts[-1].startswith("w"):
+        return None
+    try:
+        nums = [int(x) for x in parts[1:-1]] + [int(parts[-1][1:])]
+    except ValueError:
+        return None
+    if min(nums) < 1:
+        return None
+    C, P = nums[0], nums[1]
+    return (C, P, 4 * P if len(nums) == 3 else nums[2], nums[-1])
+
+
+def synthetic_name(name):
+    """`name` if it names a synthetic shape (CONFIGS or a banded one), else
+    ValueError: argparse's type= for --synthetic."""
+    if name in CONFIGS or parse_banded(name):
+        return name
+    raise ValueError(f"unknown synthetic shape {name!r}: one of {', '.join(CONFIGS)}, or banded-C-P-wW, "
+                     "banded-C-P-O-wW")
+
+
+def synthetic_named(name, seed=0xCE2E5):
+    """The arrays of a named shape: synthetic(*CONFIGS[name]) or synthetic_banded."""
+    banded = parse_banded(name)
+    if banded:
+        return synthetic_banded(*banded, seed=seed)
+    return synthetic(*CONFIGS[name], seed=seed)
+
+
+def _synthetic(num_cameras, num_points, num_observations, seed, outlier_fraction, window=None):
     C, P, O = int(num_cameras), int(num_points), int(num_observations)
     if O < P:
         raise ValueError("need at least one observation per point")
+    if window is not None and not 1 <= int(window) <= C:
+        raise ValueError("window must be in [1, num_cameras]")
     rng = np.random.Generator(np.random.PCG64(seed))
     cameras = np.empty((C, 9))
     cameras[:, 0:3] = rng.normal(0.0, 0.05, (C, 3))
@@ -87,8 +136,8 @@ def _synthetic(num_cameras, num_points, num_observations, seed, outlier_fraction
     points = rng.uniform(-3.0, 3.0, (P, 3))
 
     base, extra = divmod(O, P)
-    if base + (1 if extra else 0) > C:
-        raise ValueError("more observations per point than cameras")
+    if base + (1 if extra else 0) > (C if window is None else int(window)):
+        raise ValueError("more observations per point than cameras" + (" in a window" if window else ""))
     counts = np.full(P, base, np.int64)
     counts[:extra] += 1
     cam_idx = np.empty(O, np.int32)
@@ -99,7 +148,13 @@ def _synthetic(num_cameras, num_points, num_observations, seed, outlier_fraction
         npts = len(range(*sel.indices(P)))
         if npts == 0 or k == 0:
             continue
-        m = _distinct_rows(rng, npts, k, C)
+        if window is None:
+            m = _distinct_rows(rng, npts, k, C)
+        else:
+            W = int(window)
+            centre = rng.integers(0, C, npts, dtype=np.int64)
+            start = np.clip(centre - W // 2, 0, C - W).astype(np.int32)
+            m = _distinct_rows(rng, npts, k, W) + start[:, None]
         first = starts[sel.start]
         cam_idx[first:first + npts * k] = m.ravel()
     obs = project(cameras, points, cam_idx, pt_idx)
@@ -348,8 +403,10 @@ def synthetic_program(name_or_counts, loss=None, format=BLOCK_SPARSE, seed=0xCE2
     loss_data: per-block loss parameters (program()).  kind: another functor
     kind over the same blocks (SNAVELY_NO_DISTORTION_2_7_3 takes the first 7
     camera parameters)."""
-    counts = CONFIGS[name_or_counts] if isinstance(name_or_counts, str) else name_or_counts
-    cams, pts, ci, pi, obs = synthetic(*counts, seed=seed)
+    if isinstance(name_or_counts, str):
+        cams, pts, ci, pi, obs = synthetic_named(name_or_counts, seed=seed)  # CONFIGS, or "banded-C-P-wW"
+    else:
+        cams, pts, ci, pi, obs = synthetic(*name_or_counts, seed=seed)
     if quaternion or quaternion_manifold:
         cams = to_quaternion_cameras(cams)
     if kind == _cse.SNAVELY_NO_DISTORTION_2_7_3:

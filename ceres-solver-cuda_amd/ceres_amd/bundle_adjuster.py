@@ -40,7 +40,10 @@ def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--input", help="BAL problem file (text)")
-    src.add_argument("--synthetic", choices=list(bal.CONFIGS), help="synthetic BAL shape")
+    src.add_argument("--synthetic", type=bal.synthetic_name, metavar="SHAPE",
+                     help="synthetic BAL shape: " + ", ".join(bal.CONFIGS) + ", or one with local visibility, "
+                          "banded-C-P-wW (C cameras, P points, 4 P observations, each point's cameras from a "
+                          "window of W consecutive ones) or banded-C-P-O-wW")
     ap.add_argument("--robustify", action="store_true", help="HuberLoss(1.0)")
     ap.add_argument("--use_quaternions", action="store_true",
                     help="10-parameter cameras {q, t, f, k1, k2} (bal_problem.cc:110-121)")
@@ -71,12 +74,16 @@ def parse(argv=None):
                          "(level at 49 cameras, slower beyond): see DESIGN 3.6b")
     ap.add_argument("--preconditioner", default="jacobi",
                     choices=["identity", "jacobi", "schur_jacobi", "schur_power_series_expansion",
-                             "cluster_jacobi"],
+                             "cluster_jacobi", "cluster_tridiagonal"],
                     help="iterative_schur's preconditioner (bundle_adjuster.cc default: jacobi); "
                          "cluster_jacobi: the blocks of S over the camera clusters of "
                          "--visibility_clustering, factored once per linear solve "
                          "(cse_schur_cluster_jacobi), in the host loop and with --device_pcg; not with "
                          "--held_cameras; "
+                         "cluster_tridiagonal: besides those blocks the blocks of S between the clusters "
+                         "that a degree-2 maximum spanning forest of the cluster graph joins, factored "
+                         "along the forest's paths (cse_schur_cluster_tridiagonal), under the same flags "
+                         "and refusals; "
                          "schur_power_series_expansion: --max_num_spse_iterations terms of the series "
                          "of S^-1 per application (cse_schur_power_series), in the host loop and with "
                          "--device_pcg; not with --use_explicit_schur_complement, as the reference")
@@ -90,9 +97,10 @@ def parse(argv=None):
                          "reference's canonical_views clustering is not implemented")
     ap.add_argument("--cluster_min_similarity", type=float, default=0.9,
                     help="single_linkage's threshold (the reference's 0.9)")
-    ap.add_argument("--max_cluster_cameras", type=int, default=16,
-                    help="cameras in a cluster at most; 16 is also the most the device takes "
-                         "(one cluster is factored in one workgroup's LDS)")
+    ap.add_argument("--max_cluster_cameras", type=int, default=None,
+                    help="cameras in a cluster at most (default 16; 8 for cluster_tridiagonal); 16 is also "
+                         "the most the device takes (one cluster, or the two clusters of a forest edge, "
+                         "is factored in one workgroup's LDS)")
     ap.add_argument("--max_num_spse_iterations", type=int, default=5,
                     help="terms of the power series, for the preconditioner and for "
                          "--use_spse_initialization (bundle_adjuster.cc's flag)")
@@ -160,13 +168,15 @@ def parse(argv=None):
     if args.use_explicit_schur_complement and args.linear_solver != "iterative_schur":
         raise SystemExit("--use_explicit_schur_complement needs --linear_solver iterative_schur, not "
                          f"{args.linear_solver}")
-    if args.preconditioner == "cluster_jacobi":
+    if args.max_cluster_cameras is None:
+        args.max_cluster_cameras = 8 if args.preconditioner == "cluster_tridiagonal" else 16
+    if args.preconditioner in ("cluster_jacobi", "cluster_tridiagonal"):
         if args.linear_solver != "iterative_schur":
-            raise SystemExit("--preconditioner cluster_jacobi needs --linear_solver iterative_schur, not "
+            raise SystemExit(f"--preconditioner {args.preconditioner} needs --linear_solver iterative_schur, not "
                              f"{args.linear_solver}")
         if args.held_cameras:
-            raise SystemExit("--preconditioner cluster_jacobi does not go with --held_cameras (its pair plan "
-                             "addresses F cells by block index, as the explicit Schur complement's)")
+            raise SystemExit(f"--preconditioner {args.preconditioner} does not go with --held_cameras (its pair "
+                             "plan addresses F cells by block index, as the explicit Schur complement's)")
         if not 1 <= args.max_cluster_cameras <= 16:
             raise SystemExit("--max_cluster_cameras must be in [1, 16]")
         if not 0.0 <= args.cluster_min_similarity <= 1.0:
@@ -243,8 +253,7 @@ def solve(args, stats=None):
     if args.input:
         cams, pts, ci, pi, obs = bal.read(args.input)
     else:
-        C, P, O = bal.CONFIGS[args.synthetic]
-        cams, pts, ci, pi, obs = bal.synthetic(C, P, O)
+        cams, pts, ci, pi, obs = bal.synthetic_named(args.synthetic)
         cams, pts = cams.copy(), pts.copy()
     bal.normalize(cams, pts)
     bal.perturb(cams, pts, args.rotation_sigma, args.translation_sigma, args.point_sigma)
@@ -362,23 +371,41 @@ def solve(args, stats=None):
         e_cols, f_cols = ev.schur_structure()
         # cluster_jacobi: the init builds no preconditioner of its own (IDENTITY);
         # cse_schur_cluster_jacobi installs the cluster blocks after it.
-        cluster_pre = args.preconditioner == "cluster_jacobi"
+        tridiagonal_pre = args.preconditioner == "cluster_tridiagonal"
+        cluster_pre = args.preconditioner == "cluster_jacobi" or tridiagonal_pre
         pre = {"identity": ca._cse.SCHUR_IDENTITY, "jacobi": ca._cse.SCHUR_JACOBI,
                "schur_jacobi": ca._cse.SCHUR_SCHUR_JACOBI,
                "schur_power_series_expansion": ca._cse.SCHUR_POWER_SERIES_EXPANSION,
-               "cluster_jacobi": ca._cse.SCHUR_IDENTITY}[args.preconditioner]
+               "cluster_jacobi": ca._cse.SCHUR_IDENTITY,
+               "cluster_tridiagonal": ca._cse.SCHUR_IDENTITY}[args.preconditioner]
         if cluster_pre:
             from ceres_amd import clustering
             t0 = time.perf_counter()
             labels = clustering.cluster_cameras(ci, pi, cams.shape[0], args.visibility_clustering,
                                                 args.cluster_min_similarity, args.max_cluster_cameras)
             ev.schur_set_clusters(labels)
-            timers.add("Visibility clustering", time.perf_counter() - t0)
             sizes = np.bincount(labels)
-            print(f"cluster_jacobi: {len(sizes)} clusters of {sizes.min()} to {sizes.max()} cameras "
+            if tridiagonal_pre:
+                # The cluster graph and its degree-2 maximum spanning forest
+                # (visibility_based_preconditioner.cc:130-154).
+                forest = clustering.degree2_maximum_spanning_forest(
+                    len(sizes), *clustering.cluster_graph(ci, pi, labels), sizes=sizes)
+                ev.schur_set_cluster_forest(forest)
+                scaled_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+                scaled_solves = []
+            timers.add("Visibility clustering", time.perf_counter() - t0)
+            print(f"{args.preconditioner}: {len(sizes)} clusters of {sizes.min()} to {sizes.max()} cameras "
                   f"({args.visibility_clustering})")
+            if tridiagonal_pre:
+                paths = clustering.forest_paths(len(sizes), forest)
+                print(f"cluster_tridiagonal: {len(forest)} forest edges, {len(paths)} paths, the longest of "
+                      f"{max(len(p) for p in paths)} clusters")
             if stats is not None:
                 stats["cluster_sizes"] = sizes
+                if tridiagonal_pre:
+                    stats["forest_edges"] = forest
+                    stats["path_lengths"] = np.array([len(p) for p in paths])
+                    stats["scaled_solves"] = scaled_solves
         if pre == ca._cse.SCHUR_POWER_SERIES_EXPANSION:
             ev.schur_set_spse_iterations(args.max_num_spse_iterations)
         rhs = torch.empty(f_cols, dtype=f64, device=dev)
@@ -428,8 +455,14 @@ def solve(args, stats=None):
         # adding zeros and raised the status word (the init clears it first);
         # the next evaluation would overwrite it unread.
         if cluster_pre and ev.wait() != 0:
-            raise SystemExit("cluster_jacobi: a cluster block of S is not positive definite "
-                             "(cse_schur_cluster_jacobi raised the status word)")
+            raise SystemExit(f"{args.preconditioner}: a cluster block of S is not positive definite "
+                             f"(cse_schur_{args.preconditioner} raised the status word)")
+        if tridiagonal_pre:
+            # Whether this solve's factor ran again with the edges halved.
+            scaled_solves.append(int(scaled_flag.item()))
+            if scaled_solves[-1]:
+                print(f"cluster_tridiagonal: linear solve {len(scaled_solves)} was scaled "
+                      "(M was not positive definite; every edge block halved)")
 
     def schur_solve(lam):
         # IterativeSchurComplementSolver (iterative_schur_complement_solver.cc:
@@ -443,7 +476,10 @@ def solve(args, stats=None):
             # SolveReducedLinearSystemUsingConjugateGradients
             # (schur_complement_solver.cc): S once, then the PCG on its blocks.
             ev.schur_complement_sparse_device(S_values.data_ptr())
-        if cluster_pre:
+        if tridiagonal_pre:
+            # Preconditioner::Update: M of this S, factored along the paths.
+            ev.schur_cluster_tridiagonal_device(None, scaled_flag.data_ptr())
+        elif cluster_pre:
             # Preconditioner::Update: the cluster blocks of this S, factored.
             ev.schur_cluster_jacobi_device()
         if args.device_pcg:
@@ -613,6 +649,8 @@ def solve(args, stats=None):
     for it, c0, c1, gn, sn, rad, li, acc in rows:
         print(f"{it:4d} {c0:12.6e} {c1:12.6e} {gn:10.3e} {sn:10.3e} {rad:10.3e} {li:6d}   {acc}")
     print(f"\nInitial cost {initial_cost:.6e}  Final cost {float(cost.item()):.6e}")
+    if args.preconditioner == "cluster_tridiagonal":
+        print(f"cluster_tridiagonal: {sum(scaled_solves)} of {len(scaled_solves)} linear solves were scaled")
     print(timers.report())
     return initial_cost, float(cost.item()), rows
 

@@ -788,6 +788,31 @@ class Evaluator:
         return _cse.check(_cse.lib().cse_schur_cluster_jacobi(self.handle, d_matrices),
                           "cse_schur_cluster_jacobi")
 
+    def schur_set_cluster_forest(self, edges):
+        """The forest of CLUSTER_TRIDIAGONAL over the partition of
+        schur_set_clusters: edges[e] = (g, h), cluster labels; no cluster with
+        more than two edges, no cycle, at most _cse.SCHUR_MAX_CLUSTER_CAMERAS
+        cameras in the two clusters of an edge together
+        (cse_schur_set_cluster_forest; see
+        ceres_amd.clustering.degree2_maximum_spanning_forest).  An empty list
+        is legal.  A changed partition drops it."""
+        edges = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+        ptr = edges.ctypes.data_as(_cse.P_i32) if edges.size else None
+        return _cse.check(_cse.lib().cse_schur_set_cluster_forest(self.handle, ptr, edges.shape[0]),
+                          "cse_schur_set_cluster_forest")
+
+    def schur_cluster_tridiagonal_device(self, d_matrices=None, d_scaled=None):
+        """Forms M -- the cluster blocks of S and the blocks of the forest's
+        edges -- factors every path and makes the factor the active
+        preconditioner until the next schur_init*_device
+        (cse_schur_cluster_tridiagonal).  d_matrices: None, or room for the
+        unscaled, unfactored cells: the cluster matrices as
+        schur_cluster_jacobi_device lays them out, then (9 |g|) x (9 |h|)
+        doubles per edge in the order given.  d_scaled: None, or one int32 that
+        receives whether the factor ran a second time with the edges halved."""
+        return _cse.check(_cse.lib().cse_schur_cluster_tridiagonal(self.handle, d_matrices, d_scaled),
+                          "cse_schur_cluster_tridiagonal")
+
     def schur_back_substitute_device(self, d_x, d_y):
         """y = [(E^T E + D_e^2)^-1 E^T (b - F x); x] (BackSubstitute)."""
         return _cse.check(_cse.lib().cse_schur_back_substitute(self.handle, d_x, d_y),

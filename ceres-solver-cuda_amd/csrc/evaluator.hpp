@@ -270,6 +270,22 @@ struct cse_evaluator {
       cse::DevBuf<int64_t> first_tile, value_begin;
       cse::DevBuf<double> tiles, factor, inv_diag;
     } cluster;
+    // CLUSTER_TRIDIAGONAL (cse_schur_set_cluster_forest,
+    // cse_schur_cluster_tridiagonal): the forest as given over `cluster`'s
+    // partition, its own filtered plan and tiles (cse::PlanSchurTridiagonal;
+    // CLUSTER_JACOBI's plan is not touched), the factor, the apply's scratch
+    // and the first pass's failure flag.  A changed partition drops the forest.
+    struct Tridiagonal : cse::SchurTridiagonalCounts {
+      bool set = false, uploaded = false, active = false;
+      std::vector<int32_t> edges;
+      int64_t num_finish = 0;
+      cse::SchurPairTables tables;
+      cse::DevBuf<int32_t> tile_of_plan, plan_of_tile, tile_camera, finish;
+      cse::DevBuf<int32_t> camera_begin, cameras, d_edges, path_begin, path_cluster, path_edge;
+      cse::DevBuf<int64_t> first_tile, value_begin, edge_tile, edge_value;
+      cse::DevBuf<double> tiles, factor, inv_diag, scratch;
+      cse::DevBuf<int> failed;
+    } tridiagonal;
   } schur;
   // cse_schur_solve's scratch (cg_kernels.hpp): the four vectors p, r, z, tmp
   // in one buffer and the state, allocated by the first solve.

@@ -1070,7 +1070,7 @@ int64_t FindCgnrBlock(const CgnrBlockPlan& plan, int64_t delta, const CgnrRun** 
 }
 
 int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPlan* plan,
-                   const int32_t* cluster, int32_t first_id) {
+                   const int32_t* cluster, int32_t first_id, const int32_t* neighbor) {
   *plan = SchurPairPlan{};
   if (n >= ((int64_t)1 << 31))
     return CseFail(CSE_ERR_UNSUPPORTED, "Schur complement plan: 2^31 or more residual blocks");
@@ -1088,8 +1088,13 @@ int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPla
     const int64_t C = (int64_t)cmax - cmin + 1;
     // Pass 1: pairs per block, in a dense C x C table (upper triangle used).
     std::vector<int64_t> at((size_t)(C * C), 0);
-    // The filter: a block is kept when its two cameras carry one label.
+    // The filter: a block is kept when its two cameras carry one label, or
+    // two labels that an edge of the forest joins.
     const int32_t* label = cluster ? cluster + ((int64_t)cmin - first_id) : nullptr;
+    auto kept = [&](int64_t c, int64_t c2) {
+      if (!label || label[c] == label[c2]) return true;
+      return neighbor && (neighbor[2 * label[c]] == label[c2] || neighbor[2 * label[c] + 1] == label[c2]);
+    };
     auto each_pair = [&](auto&& f) {
       int64_t r0 = 0;
       for (int64_t i = 1; i <= n; ++i) {
@@ -1098,7 +1103,7 @@ int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPla
           const int64_t c = ids[2 * b] - cmin;
           for (int64_t b2 = r0; b2 < i; ++b2) {
             const int64_t c2 = ids[2 * b2] - cmin;
-            if (c <= c2 && (!label || label[c] == label[c2])) f(c * C + c2, b, b2);
+            if (c <= c2 && kept(c, c2)) f(c * C + c2, b, b2);
           }
         }
         r0 = i;
@@ -1327,6 +1332,235 @@ int PlanSchurClusters(const int32_t* ids, int64_t n, int32_t first_id, int64_t C
   } catch (const std::bad_alloc&) {
     *plan = SchurClusterPlan{};
     return CseFail(CSE_ERR_OOM, "cluster plan: host allocation failed");
+  }
+  return CSE_OK;
+}
+
+int ValidateSchurForest(const int32_t* edges, int32_t num_edges, const int32_t* size, int32_t num_clusters,
+                        SchurForestPaths* paths) {
+  *paths = SchurForestPaths{};
+  if (num_edges < 0) return CseFail(CSE_ERR_INVALID, "cluster forest: negative num_edges");
+  if (num_edges > 0 && !edges) return CseFail(CSE_ERR_INVALID, "cluster forest: null edges");
+  auto name = [&](int32_t e) {
+    return "edge " + std::to_string(e) + " (" + std::to_string(edges[2 * e]) + ", " +
+           std::to_string(edges[2 * e + 1]) + ")";
+  };
+  try {
+    std::vector<int32_t>& nb = paths->neighbor;
+    nb.assign((size_t)(2 * (int64_t)num_clusters), -1);
+    std::vector<int32_t> nb_edge(nb.size(), -1);
+    for (int32_t e = 0; e < num_edges; ++e) {
+      const int32_t g = edges[2 * e], h = edges[2 * e + 1];
+      if (g < 0 || g >= num_clusters || h < 0 || h >= num_clusters)
+        return CseFail(CSE_ERR_INVALID, "cluster forest: " + name(e) + " has a label outside [0, " +
+                                            std::to_string(num_clusters) + ")");
+      if (g == h) return CseFail(CSE_ERR_INVALID, "cluster forest: " + name(e) + " joins a cluster to itself");
+    }
+    // Duplicates, in either orientation, before degrees: an edge given twice
+    // is invalid whatever else the list holds.
+    {
+      std::vector<std::pair<std::pair<int32_t, int32_t>, int32_t>> sorted;
+      sorted.reserve((size_t)num_edges);
+      for (int32_t e = 0; e < num_edges; ++e)
+        sorted.push_back({{std::min(edges[2 * e], edges[2 * e + 1]), std::max(edges[2 * e], edges[2 * e + 1])}, e});
+      std::sort(sorted.begin(), sorted.end());
+      for (size_t i = 1; i < sorted.size(); ++i)
+        if (sorted[i].first == sorted[i - 1].first)
+          return CseFail(CSE_ERR_INVALID, "cluster forest: " + name(sorted[i].second) + " is given twice (as edge " +
+                                              std::to_string(sorted[i - 1].second) + ")");
+    }
+    for (int32_t e = 0; e < num_edges; ++e) {
+      const int32_t g = edges[2 * e], h = edges[2 * e + 1];
+      for (int32_t v : {g, h}) {
+        const int32_t w = v == g ? h : g;
+        int32_t* slot = &nb[2 * (size_t)v];
+        const int at = slot[0] < 0 ? 0 : slot[1] < 0 ? 1 : 2;
+        if (at == 2) {
+          return CseFail(CSE_ERR_UNSUPPORTED, "cluster forest: cluster " + std::to_string(v) +
+                                                  " has three edges (" + name(e) +
+                                                  " is the third); every tree must be a path");
+        }
+        slot[at] = w;
+        nb_edge[2 * (size_t)v + at] = e;
+      }
+    }
+    for (int32_t e = 0; e < num_edges; ++e) {
+      const int64_t sum = (int64_t)size[edges[2 * e]] + size[edges[2 * e + 1]];
+      if (sum > kSchurMaxClusterCameras)
+        return CseFail(CSE_ERR_UNSUPPORTED,
+                       "cluster forest: the clusters of " + name(e) + " hold " + std::to_string(sum) +
+                           " cameras together, more than " + std::to_string(kSchurMaxClusterCameras) +
+                           " (one elimination step works in the LDS of one workgroup)");
+    }
+    // The paths: from every cluster of degree < 2 not yet visited, in label
+    // order, so a path starts at its end with the smaller label and the paths
+    // come ordered by their first cluster.
+    std::vector<bool> visited((size_t)num_clusters, false);
+    paths->path_begin.assign(1, 0);
+    for (int32_t g = 0; g < num_clusters; ++g) {
+      if (visited[(size_t)g] || nb[2 * (size_t)g + 1] >= 0) continue;
+      int32_t prev = -1, at = g;
+      while (at >= 0) {
+        visited[(size_t)at] = true;
+        const int which = nb[2 * (size_t)at] >= 0 && nb[2 * (size_t)at] != prev ? 0
+                          : nb[2 * (size_t)at + 1] >= 0 && nb[2 * (size_t)at + 1] != prev ? 1 : -1;
+        paths->path_cluster.push_back(at);
+        if (which < 0) {
+          paths->path_edge.push_back(-1);
+          break;
+        }
+        const int32_t e = nb_edge[2 * (size_t)at + which];
+        paths->path_edge.push_back(2 * e + (edges[2 * e + 1] == at ? 1 : 0));
+        prev = at;
+        at = nb[2 * (size_t)at + which];
+      }
+      paths->path_begin.push_back((int32_t)paths->path_cluster.size());
+    }
+    // What is left has degree 2 throughout: a cycle.
+    for (int32_t g = 0; g < num_clusters; ++g)
+      if (!visited[(size_t)g])
+        return CseFail(CSE_ERR_UNSUPPORTED, "cluster forest: cluster " + std::to_string(g) +
+                                                " lies on a cycle; every tree must be a path");
+  } catch (const std::bad_alloc&) {
+    *paths = SchurForestPaths{};
+    return CseFail(CSE_ERR_OOM, "cluster forest: host allocation failed");
+  }
+  return CSE_OK;
+}
+
+int PlanSchurTridiagonal(const int32_t* ids, int64_t n, int32_t first_id, int64_t C, const int32_t* cluster,
+                         int32_t num_clusters, const int32_t* edges, int32_t num_edges, bool counts_only,
+                         SchurTridiagonalPlan* plan) {
+  *plan = SchurTridiagonalPlan{};
+  int rc = ValidateSchurClusters(cluster, C, num_clusters);
+  if (rc) return rc;
+  try {
+    std::vector<int32_t> size((size_t)num_clusters, 0);
+    for (int64_t c = 0; c < C; ++c) ++size[(size_t)cluster[c]];
+    SchurTridiagonalPlan& Z = *plan;
+    if ((rc = ValidateSchurForest(edges, num_edges, size.data(), num_clusters, &Z.paths))) return rc;
+    std::vector<bool> seen((size_t)C, false);
+    int64_t unobserved = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t c = (int64_t)ids[2 * i] - first_id;
+      if (c < 0 || c >= C) return CseFail(CSE_ERR_INVALID, "tridiagonal plan: an f block outside the cameras");
+      seen[(size_t)c] = true;
+    }
+    for (int64_t c = 0; c < C; ++c)
+      if (!seen[(size_t)c]) ++unobserved;
+    if ((rc = PlanSchurPairs(ids, n, counts_only, &Z.pairs, cluster, first_id, Z.paths.neighbor.data()))) return rc;
+    Z.num_clusters = num_clusters;
+    Z.num_cameras = C;
+    Z.num_edges = num_edges;
+    Z.num_paths = (int64_t)Z.paths.path_begin.size() - 1;
+    for (int32_t g = 0; g < num_clusters; ++g) {
+      const int64_t ng = size[(size_t)g];
+      Z.num_cluster_tiles += ng * (ng + 1) / 2;
+      Z.num_values += 81 * ng * ng;
+      Z.max_cameras = std::max(Z.max_cameras, ng);
+    }
+    Z.num_tiles = Z.num_cluster_tiles;
+    Z.max_step_cameras = Z.max_cameras;
+    for (int32_t e = 0; e < num_edges; ++e) {
+      const int64_t ng = size[(size_t)edges[2 * e]], nh = size[(size_t)edges[2 * e + 1]];
+      Z.num_tiles += ng * nh;
+      Z.num_values += 81 * ng * nh;
+      Z.max_step_cameras = std::max(Z.max_step_cameras, ng + nh);
+    }
+    for (int64_t p = 0; p < Z.num_paths; ++p)
+      Z.longest_path = std::max<int64_t>(Z.longest_path, Z.paths.path_begin[(size_t)p + 1] - Z.paths.path_begin[(size_t)p]);
+    if (Z.num_tiles >= ((int64_t)1 << 31))
+      return CseFail(CSE_ERR_UNSUPPORTED, "tridiagonal plan: 2^31 or more tiles");
+    Z.finish_capacity = Z.pairs.num_chunks - Z.pairs.num_blocks + unobserved;
+    if (counts_only) return CSE_OK;
+    Z.camera_begin.assign((size_t)num_clusters + 1, 0);
+    Z.first_tile.assign((size_t)num_clusters + 1, 0);
+    Z.value_begin.assign((size_t)num_clusters + 1, 0);
+    for (int32_t g = 0; g < num_clusters; ++g) {
+      const int64_t ng = size[(size_t)g];
+      Z.camera_begin[(size_t)g + 1] = Z.camera_begin[(size_t)g] + (int32_t)ng;
+      Z.first_tile[(size_t)g + 1] = Z.first_tile[(size_t)g] + ng * (ng + 1) / 2;
+      Z.value_begin[(size_t)g + 1] = Z.value_begin[(size_t)g] + 81 * ng * ng;
+    }
+    Z.edges.assign(edges, edges + 2 * (size_t)num_edges);
+    Z.edge_tile.assign((size_t)num_edges + 1, Z.num_cluster_tiles);
+    Z.edge_value.assign((size_t)num_edges + 1, Z.value_begin[(size_t)num_clusters]);
+    for (int32_t e = 0; e < num_edges; ++e) {
+      const int64_t cells = (int64_t)size[(size_t)edges[2 * e]] * size[(size_t)edges[2 * e + 1]];
+      Z.edge_tile[(size_t)e + 1] = Z.edge_tile[(size_t)e] + cells;
+      Z.edge_value[(size_t)e + 1] = Z.edge_value[(size_t)e] + 81 * cells;
+    }
+    Z.cameras.resize((size_t)C);
+    std::vector<int32_t> local((size_t)C), cursor(Z.camera_begin.begin(), Z.camera_begin.end() - 1);
+    for (int64_t c = 0; c < C; ++c) {
+      const int32_t g = cluster[c];
+      local[(size_t)c] = cursor[(size_t)g] - Z.camera_begin[(size_t)g];
+      Z.cameras[(size_t)cursor[(size_t)g]++] = (int32_t)c;
+    }
+    Z.plan_of_tile.assign((size_t)Z.num_tiles, -1);
+    Z.tile_camera.resize((size_t)Z.num_tiles);
+    for (int32_t g = 0; g < num_clusters; ++g)
+      for (int32_t j = 0; j < size[(size_t)g]; ++j)
+        for (int32_t i = 0; i <= j; ++i)
+          Z.tile_camera[(size_t)(Z.first_tile[(size_t)g] + ClusterTile(i, j))] =
+              Z.cameras[(size_t)(Z.camera_begin[(size_t)g] + i)];
+    for (int32_t e = 0; e < num_edges; ++e) {
+      const int32_t g = edges[2 * e], nh = size[(size_t)edges[2 * e + 1]];
+      for (int32_t i = 0; i < size[(size_t)g]; ++i)
+        for (int32_t j = 0; j < nh; ++j)  // not read: only an empty diagonal tile's camera is
+          Z.tile_camera[(size_t)(Z.edge_tile[(size_t)e] + (int64_t)i * nh + j)] =
+              Z.cameras[(size_t)(Z.camera_begin[(size_t)g] + i)];
+    }
+    // The edge of two joined labels, by the smaller label's neighbour slot.
+    auto edge_of = [&](int32_t a, int32_t b) {
+      for (int32_t e = 0; e < num_edges; ++e)
+        if ((edges[2 * e] == a && edges[2 * e + 1] == b) || (edges[2 * e] == b && edges[2 * e + 1] == a)) return e;
+      return (int32_t)-1;
+    };
+    std::vector<int32_t> slot_edge((size_t)(2 * (int64_t)num_clusters), -1);
+    for (int32_t g = 0; g < num_clusters; ++g)
+      for (int s = 0; s < 2; ++s)
+        if (Z.paths.neighbor[2 * (size_t)g + s] >= 0 && Z.paths.neighbor[2 * (size_t)g + s] > g)
+          slot_edge[2 * (size_t)g + s] = edge_of(g, Z.paths.neighbor[2 * (size_t)g + s]);
+    Z.tile_of_plan.resize((size_t)Z.pairs.num_blocks);
+    for (int64_t k = 0; k < Z.pairs.num_blocks; ++k) {
+      const int64_t c = (int64_t)Z.pairs.block_row[(size_t)k] - first_id;
+      const int64_t c2 = (int64_t)Z.pairs.block_col[(size_t)k] - first_id;
+      const int32_t l = cluster[c], l2 = cluster[c2];
+      int64_t t;
+      if (l == l2) {
+        t = Z.first_tile[(size_t)l] + ClusterTile(local[(size_t)c], local[(size_t)c2]);
+      } else {
+        const int32_t lo = std::min(l, l2), hi = std::max(l, l2);
+        const int s = Z.paths.neighbor[2 * (size_t)lo] == hi ? 0 : 1;
+        const int32_t e = slot_edge[2 * (size_t)lo + s];
+        if (e < 0) return CseFail(CSE_ERR_INVALID, "tridiagonal plan: a kept block without an edge");
+        // The camera of the edge's g gives the rectangle's row.
+        const int64_t cg = edges[2 * e] == l ? c : c2, ch = edges[2 * e] == l ? c2 : c;
+        t = Z.edge_tile[(size_t)e] + (int64_t)local[(size_t)cg] * size[(size_t)edges[2 * e + 1]] + local[(size_t)ch];
+      }
+      Z.tile_of_plan[(size_t)k] = (int32_t)t;
+      Z.plan_of_tile[(size_t)t] = (int32_t)k;
+    }
+    for (int64_t t = 0; t < Z.num_tiles; ++t) {
+      const int64_t k = Z.plan_of_tile[(size_t)t];
+      if (k < 0) {
+        Z.empty_tiles.push_back((int32_t)t);
+        continue;
+      }
+      if (Z.pairs.chunk_off[(size_t)k + 1] - Z.pairs.chunk_off[(size_t)k] != 1) Z.finish.push_back((int32_t)t);
+    }
+    // A diagonal tile no block writes: the camera has no residual block.
+    for (int32_t g = 0; g < num_clusters; ++g)
+      for (int32_t j = 0; j < size[(size_t)g]; ++j) {
+        const int64_t t = Z.first_tile[(size_t)g] + ClusterTile(j, j);
+        if (Z.plan_of_tile[(size_t)t] < 0) Z.finish.push_back((int32_t)t);
+      }
+    if ((int64_t)Z.finish.size() > Z.finish_capacity)
+      return CseFail(CSE_ERR_INVALID, "tridiagonal plan: the finish list exceeds its bound");
+  } catch (const std::bad_alloc&) {
+    *plan = SchurTridiagonalPlan{};
+    return CseFail(CSE_ERR_OOM, "tridiagonal plan: host allocation failed");
   }
   return CSE_OK;
 }

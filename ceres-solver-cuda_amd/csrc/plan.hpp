@@ -347,8 +347,11 @@ struct SchurPairPlan : SchurPairCounts {
 // block id; only the blocks whose two f blocks carry one label are kept.  A
 // kept block's pairs, their order and its chunk cut are the unfiltered
 // plan's (the same walk with the other blocks' counts left at zero).
+// neighbor (may be null; needs cluster): [labels][2], the labels a cluster is
+// joined to by an edge of the cluster forest (-1: none); a block whose two
+// labels are joined is kept too (CLUSTER_TRIDIAGONAL).
 int PlanSchurPairs(const int32_t* ids, int64_t n, bool counts_only, SchurPairPlan* plan,
-                   const int32_t* cluster = nullptr, int32_t first_id = 0);
+                   const int32_t* cluster = nullptr, int32_t first_id = 0, const int32_t* neighbor = nullptr);
 
 // ---- CLUSTER_JACOBI (cse_schur_set_clusters, cse_schur_cluster_jacobi): the
 // cluster-filtered pair plan and where its blocks go.  Cluster g of n_g
@@ -388,6 +391,58 @@ struct SchurClusterPlan : SchurClusterCounts {
 int ValidateSchurClusters(const int32_t* cluster, int64_t C, int32_t num_clusters);
 int PlanSchurClusters(const int32_t* ids, int64_t n, int32_t first_id, int64_t C, const int32_t* cluster,
                       int32_t num_clusters, bool counts_only, SchurClusterPlan* plan);
+
+// ---- CLUSTER_TRIDIAGONAL (cse_schur_set_cluster_forest,
+// cse_schur_cluster_tridiagonal): the partition above and a forest over its
+// clusters in which every cluster has at most two edges, so that each tree is
+// a path.  M keeps S's blocks inside a cluster and between the two clusters of
+// an edge; in path order it is block tridiagonal.
+//
+// The tiles: the clusters' triangles exactly as SchurClusterPlan lays them
+// out (tiles [0, first_tile[num_clusters])), then per edge e = (g, h), as it
+// was given, a rectangle of n_g n_h tiles from edge_tile[e]: tile
+// edge_tile[e] + i n_h + j belongs to the cameras a = (camera i of g) and
+// b = (camera j of h) and HOLDS S(min(a, b), max(a, b)), the plan's block,
+// row-major as the block store writes it.  So it is S(a, b) when a < b and its
+// transpose otherwise; the kernels compare the two camera indices.  An edge's
+// two clusters hold at most kSchurMaxClusterCameras cameras together: one
+// elimination step works on their combined triangle in one workgroup's LDS.
+struct SchurForestPaths {
+  // Path p is path_cluster[path_begin[p] .. path_begin[p + 1]), listed from its
+  // end with the smaller label; the paths are ordered by their first cluster; a
+  // cluster without an edge is a path of one.  path_edge[q] joins
+  // path_cluster[q] and path_cluster[q + 1]: 2 e + flip, flip = 1 when
+  // path_cluster[q] is the edge's h; -1 at a path's last cluster.
+  std::vector<int32_t> path_begin, path_cluster, path_edge;
+  std::vector<int32_t> neighbor;  // [num_clusters][2], -1 = none
+};
+// edges: [num_edges][2] labels.  size[g] = cameras of cluster g.
+// CSE_ERR_INVALID: null edges with num_edges > 0, a label out of range, g = h,
+// a duplicate (in either orientation).  CSE_ERR_UNSUPPORTED, naming the
+// cluster or edge: a cluster with three edges, a cycle, an edge whose clusters
+// hold more than kSchurMaxClusterCameras cameras together.
+int ValidateSchurForest(const int32_t* edges, int32_t num_edges, const int32_t* size, int32_t num_clusters,
+                        SchurForestPaths* paths);
+
+struct SchurTridiagonalCounts : SchurClusterCounts {
+  // num_tiles, num_values: the clusters' and the edges' together.
+  int64_t num_edges = 0, num_paths = 0;
+  int64_t num_cluster_tiles = 0;  // the clusters' triangles: the edges' rectangles follow
+  int64_t max_step_cameras = 0;   // the most cameras one elimination step holds: an edge's two clusters, or a lone cluster
+  int64_t longest_path = 0;       // clusters
+};
+struct SchurTridiagonalPlan : SchurTridiagonalCounts {
+  SchurPairPlan pairs;                // the filtered plan: one label, or the two labels of an edge
+  std::vector<int32_t> camera_begin, cameras;
+  std::vector<int64_t> first_tile, value_begin;   // per cluster, as SchurClusterPlan's
+  std::vector<int32_t> edges;                     // [num_edges][2] as given
+  std::vector<int64_t> edge_tile, edge_value;     // [num_edges + 1]: first tile; offset of S[g, h] in the matrices
+  SchurForestPaths paths;
+  std::vector<int32_t> tile_of_plan, plan_of_tile, tile_camera, finish, empty_tiles;  // as SchurClusterPlan's
+};
+int PlanSchurTridiagonal(const int32_t* ids, int64_t n, int32_t first_id, int64_t C, const int32_t* cluster,
+                         int32_t num_clusters, const int32_t* edges, int32_t num_edges, bool counts_only,
+                         SchurTridiagonalPlan* plan);
 
 // ---- The block-sparse Schur complement (cse_schur_complement_sparse,
 // cse_schur_explicit_multiply): S's upper triangle as block-compressed rows,

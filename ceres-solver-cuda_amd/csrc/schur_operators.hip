@@ -1,8 +1,8 @@
 // schur_operators.hip -- the cse_schur_* calls of the C ABI (include/cse.h) on
 // the evaluator (evaluator.hpp): the implicit Schur complement and the power
 // series (schur_kernels.hpp), the pair, sparse and cluster plans, the explicit
-// complements (schur_complement_kernels.hpp), CLUSTER_JACOBI
-// (cluster_kernels.hpp) and cse_schur_solve (cg_solve.hpp; the vector kernels
+// complements (schur_complement_kernels.hpp), CLUSTER_JACOBI and
+// CLUSTER_TRIDIAGONAL (cluster_kernels.hpp) and cse_schur_solve (cg_solve.hpp; the vector kernels
 // through cg_kernels.h).  The per-camera sums are launched through
 // evaluator.hpp's LaunchContribReduce: their kernels stay instantiated in
 // cse_evaluator.hip.
@@ -242,6 +242,7 @@ int SchurInit(cse_evaluator* ev, const double* d_jacobian_values, const double* 
   S.ub_grad = grad;
   ev->spse.blocks_ready = false;  // cse_schur_power_series builds its own after IDENTITY / SCHUR_JACOBI
   S.cluster.active = false;       // the init's own preconditioner is back
+  S.tridiagonal.active = false;
   // Point order: M_p, u_b = b_b - E_b M_p E_b^T b (and the gradient's e
   // rows); then camera order: rhs = F^T u, the gradient's f rows -F^T b and
   // the preconditioner's F^T Q F, each F cell read once.  The status word
@@ -596,6 +597,106 @@ void LaunchClusterApply(cse_evaluator* ev, const double* x, double* y, bool accu
 }
 
 // ---------------------------------------------------------------------------
+// CLUSTER_TRIDIAGONAL (cluster_kernels.hpp; cse::PlanSchurTridiagonal)
+// ---------------------------------------------------------------------------
+// The forest's filtered plan, tile layout and paths, built and uploaded once
+// per forest (by cse_schur_set_cluster_forest).
+int SchurTridiagonalPlanOf(cse_evaluator* ev) {
+  auto& T = ev->schur.tridiagonal;
+  const auto& K = ev->schur.cluster;
+  if (T.uploaded) return CSE_OK;
+  const Group& G = ev->groups[0];
+  std::vector<int32_t> ids;
+  int rc = SchurIds(ev, &ids);
+  if (rc) return rc;
+  int32_t first_id;
+  int64_t C;
+  SchurCameraIndex(ev, &first_id, &C);
+  cse::SchurTridiagonalPlan P;
+  if ((rc = cse::PlanSchurTridiagonal(ids.data(), G.n, first_id, C, K.labels.data(), K.num_labels, T.edges.data(),
+                                      (int32_t)(T.edges.size() / 2), false, &P)))
+    return rc;
+  hipStream_t s = ev->stream;
+  rc = T.tables.Upload(P.pairs, s);
+  if (!rc) rc = T.tile_of_plan.upload(P.tile_of_plan.data(), P.tile_of_plan.size(), s);
+  if (!rc) rc = T.plan_of_tile.upload(P.plan_of_tile.data(), P.plan_of_tile.size(), s);
+  if (!rc) rc = T.tile_camera.upload(P.tile_camera.data(), P.tile_camera.size(), s);
+  if (!rc) rc = T.finish.upload(P.finish.data(), P.finish.size(), s);
+  if (!rc) rc = T.camera_begin.upload(P.camera_begin.data(), P.camera_begin.size(), s);
+  if (!rc) rc = T.cameras.upload(P.cameras.data(), P.cameras.size(), s);
+  if (!rc) rc = T.first_tile.upload(P.first_tile.data(), P.first_tile.size(), s);
+  if (!rc) rc = T.value_begin.upload(P.value_begin.data(), P.value_begin.size(), s);
+  if (!rc) rc = T.d_edges.upload(P.edges.data(), P.edges.size(), s);
+  if (!rc) rc = T.edge_tile.upload(P.edge_tile.data(), P.edge_tile.size(), s);
+  if (!rc) rc = T.edge_value.upload(P.edge_value.data(), P.edge_value.size(), s);
+  if (!rc) rc = T.path_begin.upload(P.paths.path_begin.data(), P.paths.path_begin.size(), s);
+  if (!rc) rc = T.path_cluster.upload(P.paths.path_cluster.data(), P.paths.path_cluster.size(), s);
+  if (!rc) rc = T.path_edge.upload(P.paths.path_edge.data(), P.paths.path_edge.size(), s);
+  if (!rc) rc = T.tiles.ensure((size_t)std::max<int64_t>(1, P.num_tiles * cse::kSchurBlockDoubles));
+  if (!rc) rc = T.factor.ensure((size_t)std::max<int64_t>(1, P.num_tiles * cse::kSchurBlockDoubles));
+  if (!rc) rc = T.inv_diag.ensure((size_t)std::max<int64_t>(1, 9 * C));
+  if (!rc) rc = T.scratch.ensure((size_t)std::max<int64_t>(1, 9 * C));
+  if (!rc) rc = T.failed.ensure(1);
+  // The copies read P's tables: wait before P goes out of scope.
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = Fail(CSE_ERR_HIP, "tridiagonal plan upload failed");
+  if (rc) {
+    T.tables.Release();
+    return rc;
+  }
+  static_cast<cse::SchurTridiagonalCounts&>(T) = P;
+  T.num_finish = (int64_t)P.finish.size();
+  // One step in one workgroup's LDS: above 64 KiB the kernels need the limit raised.
+  CSE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&cse::TridiagonalFactorKernel<9>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)cse::ClusterFactorLds(cse::kSchurMaxClusterCameras)));
+  CSE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&cse::TridiagonalApplyKernel<9>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)cse::TridiagonalApplyLds(cse::kSchurMaxClusterCameras)));
+  T.uploaded = true;
+  return CSE_OK;
+}
+
+cse::TridiagonalArgs MakeTridiagonalArgs(cse_evaluator* ev) {
+  const auto& T = ev->schur.tridiagonal;
+  cse::TridiagonalArgs a{};
+  a.camera_begin = T.camera_begin.p;
+  a.cameras = T.cameras.p;
+  a.first_tile = T.first_tile.p;
+  a.value_begin = T.value_begin.p;
+  a.edges = T.d_edges.p;
+  a.edge_tile = T.edge_tile.p;
+  a.edge_value = T.edge_value.p;
+  a.path_begin = T.path_begin.p;
+  a.path_cluster = T.path_cluster.p;
+  a.path_edge = T.path_edge.p;
+  a.tiles = T.tiles.p;
+  a.factor = T.factor.p;
+  a.inv_diag = T.inv_diag.p;
+  a.scratch = T.scratch.p;
+  a.failed = T.failed.p;
+  a.status = ev->status.p + 1;
+  a.max_step = (int)T.max_step_cameras;
+  return a;
+}
+
+// y (+)= M^-1 x over every path; every f entry belongs to one path.
+void LaunchTridiagonalApply(cse_evaluator* ev, const double* x, double* y, bool accumulate) {
+  const auto& T = ev->schur.tridiagonal;
+  if (T.num_paths <= 0) return;
+  hipLaunchKernelGGL((cse::TridiagonalApplyKernel<9>), dim3((unsigned)T.num_paths), dim3(cse::kClusterThreads),
+                     cse::TridiagonalApplyLds(T.max_step_cameras), ev->stream, MakeTridiagonalArgs(ev), x, y,
+                     accumulate ? 1 : 0);
+}
+
+// Whichever cluster preconditioner is active.
+void LaunchActiveClusterApply(cse_evaluator* ev, const double* x, double* y, bool accumulate) {
+  if (ev->schur.tridiagonal.active)
+    LaunchTridiagonalApply(ev, x, y, accumulate);
+  else
+    LaunchClusterApply(ev, x, y, accumulate);
+}
+
+// ---------------------------------------------------------------------------
 // cse_schur_solve (cg_solve.hpp)
 // ---------------------------------------------------------------------------
 // cg_kernels.hpp's one-workgroup kernels, and how z = M^-1 r is produced, a
@@ -614,7 +715,7 @@ struct SchurCgLaunch {
     switch (how) {
       case kInKernel: cse::LaunchCgDirection(a, s); return;
       case kSeries: (void)SpseEnqueue(ev, ev->schur.spse_iterations, 0.0, a.r, a.z, false); break;
-      case kClusters: LaunchClusterApply(ev, a.r, a.z, false); break;
+      case kClusters: LaunchActiveClusterApply(ev, a.r, a.z, false); break;
     }
     cse::LaunchCgDirectionGiven(a, s);
   }
@@ -667,8 +768,8 @@ int cse_schur_precondition(cse_evaluator* ev, const double* d_x, double* d_y) {
   if (!d_x || !d_y) return Fail(CSE_ERR_INVALID, "null pointer");
   const auto& S = ev->schur;
   hipStream_t s = ev->stream;
-  if (S.cluster.active) {  // CLUSTER_JACOBI: y += M^-1 x by the factor
-    LaunchClusterApply(ev, d_x, d_y, true);
+  if (S.cluster.active || S.tridiagonal.active) {  // CLUSTER_JACOBI / _TRIDIAGONAL: y += M^-1 x by the factor
+    LaunchActiveClusterApply(ev, d_x, d_y, true);
     CSE_HIP(hipGetLastError());
     return CSE_OK;
   }
@@ -875,6 +976,10 @@ int cse_schur_set_clusters(cse_evaluator* ev, const int32_t* cluster_of_camera, 
   K.num_labels = num_clusters;
   K.uploaded = false;
   K.active = false;  // a factor of the earlier partition
+  // The forest was one over the earlier partition's clusters: dropped.
+  auto& T = ev->schur.tridiagonal;
+  T.set = T.uploaded = T.active = false;
+  T.edges.clear();
   // The filtered plan and the tile layout now, on the host, so that no linear
   // solve pays for them.
   K.set = true;
@@ -911,6 +1016,78 @@ int cse_schur_cluster_jacobi(cse_evaluator* ev, double* d_matrices) {
   }
   CSE_HIP(hipGetLastError());
   K.active = true;
+  S.tridiagonal.active = false;  // the latest build is the active one
+  return CSE_OK;
+}
+
+int cse_schur_set_cluster_forest(cse_evaluator* ev, const int32_t* edges, int32_t num_edges) {
+  int rc = SchurClusterCheck(ev, "cse_schur_set_cluster_forest");
+  if (rc) return rc;
+  auto& K = ev->schur.cluster;
+  auto& T = ev->schur.tridiagonal;
+  if (!K.set) return Fail(CSE_ERR_INVALID, "cse_schur_set_cluster_forest: cse_schur_set_clusters has not run");
+  if (num_edges < 0) return Fail(CSE_ERR_INVALID, "cse_schur_set_cluster_forest: negative num_edges");
+  if (num_edges > 0 && !edges) return Fail(CSE_ERR_INVALID, "cse_schur_set_cluster_forest: null edges");
+  // Refusals first, so that a refused forest leaves the one in place as it is.
+  try {
+    std::vector<int32_t> size((size_t)K.num_labels, 0);
+    for (int32_t l : K.labels) ++size[(size_t)l];
+    cse::SchurForestPaths paths;
+    if ((rc = cse::ValidateSchurForest(edges, num_edges, size.data(), K.num_labels, &paths))) return rc;
+    if (T.set && (int64_t)T.edges.size() == 2LL * num_edges && std::equal(T.edges.begin(), T.edges.end(), edges))
+      return CSE_OK;
+    T.edges.assign(edges, edges + 2 * (size_t)num_edges);
+  } catch (const std::bad_alloc&) {
+    T.set = false;
+    return Fail(CSE_ERR_OOM, "cse_schur_set_cluster_forest: host allocation failed");
+  }
+  T.uploaded = false;
+  T.active = false;  // a factor over the earlier forest
+  T.set = true;
+  if ((rc = SchurTridiagonalPlanOf(ev))) T.set = false;
+  return rc;
+}
+
+int cse_schur_cluster_tridiagonal(cse_evaluator* ev, double* d_matrices, int32_t* d_scaled) {
+  int rc = SchurClusterCheck(ev, "cse_schur_cluster_tridiagonal");
+  if (rc) return rc;
+  auto& S = ev->schur;
+  auto& T = S.tridiagonal;
+  if (!S.ready) return Fail(CSE_ERR_INVALID, "cse_schur_cluster_tridiagonal: cse_schur_init has not run");
+  if (!S.cluster.set)
+    return Fail(CSE_ERR_INVALID, "cse_schur_cluster_tridiagonal: cse_schur_set_clusters has not run");
+  if (!T.set)
+    return Fail(CSE_ERR_INVALID,
+                "cse_schur_cluster_tridiagonal: cse_schur_set_cluster_forest has not run for this partition "
+                "(a changed partition drops the forest)");
+  if ((rc = SchurTridiagonalPlanOf(ev))) return rc;
+  hipStream_t s = ev->stream;
+  // The cells, off-diagonal ones included, by the explicit complement's
+  // kernels over the filtered plan; the tiles no block writes are zero.
+  cse::SchurPairArgs a = MakeSchurPairArgs(ev, T.tables);
+  a.sparse_of_plan = T.tile_of_plan.p;
+  a.plan_block = T.plan_of_tile.p;
+  a.sparse_col = T.tile_camera.p;
+  a.finish = T.finish.p;
+  a.nfinish = T.num_finish;
+  a.values = T.tiles.p;
+  if (T.num_tiles > 0)
+    CSE_HIP(hipMemsetAsync(T.tiles.p, 0, (size_t)T.num_tiles * cse::kSchurBlockDoubles * sizeof(double), s));
+  CSE_HIP(hipMemsetAsync(T.failed.p, 0, sizeof(int), s));
+  LaunchSchurBlockStore(a, s);
+  if (T.num_paths > 0) {
+    cse::TridiagonalArgs c = MakeTridiagonalArgs(ev);
+    c.matrices = d_matrices;
+    // M as it is; then, only when a pivot failed, every path again with its
+    // edges halved: the second launch decides on the device.
+    for (int scaled = 0; scaled < 2; ++scaled)
+      hipLaunchKernelGGL((cse::TridiagonalFactorKernel<9>), dim3((unsigned)T.num_paths), dim3(cse::kClusterThreads),
+                         cse::ClusterFactorLds(T.max_step_cameras), s, c, scaled);
+  }
+  CSE_HIP(hipGetLastError());
+  if (d_scaled) CSE_HIP(hipMemcpyAsync(d_scaled, T.failed.p, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  T.active = true;
+  S.cluster.active = false;  // the latest build is the active one
   return CSE_OK;
 }
 
@@ -929,8 +1106,9 @@ int cse_schur_solve(cse_evaluator* ev, const cse_cg_options* options, const doub
     return Fail(CSE_ERR_UNSUPPORTED,
                 "cse_schur_solve: d_S_values (the explicit Schur complement) is not available with held "
                 "cameras (constant slot-0 blocks); pass NULL for the implicit operator");
-  const bool series = !S.cluster.active && S.preconditioner == CSE_SCHUR_POWER_SERIES_EXPANSION;
-  const auto how = S.cluster.active ? SchurCgLaunch::kClusters
+  const bool clusters = S.cluster.active || S.tridiagonal.active;
+  const bool series = !clusters && S.preconditioner == CSE_SCHUR_POWER_SERIES_EXPANSION;
+  const auto how = clusters ? SchurCgLaunch::kClusters
                    : series         ? SchurCgLaunch::kSeries
                                     : SchurCgLaunch::kInKernel;
   if (d_S_values && series)

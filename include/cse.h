@@ -651,6 +651,55 @@ int cse_schur_set_clusters(cse_evaluator* ev, const int32_t* cluster_of_camera,
  * cse_schur_set_clusters. */
 int cse_schur_cluster_jacobi(cse_evaluator* ev, double* d_matrices /* may be NULL */);
 
+/* ---- CLUSTER_TRIDIAGONAL ---------------------------------------------------
+ * The reference's second visibility-based preconditioner
+ * (visibility_based_preconditioner.cc:130-154, 318-390): besides the cluster
+ * blocks M_gg = S[g, g] it keeps M_gh = S[g, h] for the edges (g, h) of a
+ * forest over the clusters in which no cluster has more than two edges
+ * (Degree2MaximumSpanningForest; ceres_amd/clustering.py computes it).  Every
+ * tree of such a forest is a path, and along a path M is block tridiagonal; one
+ * workgroup factors a path and one applies it.  One elimination step holds
+ * the two clusters of an edge in the LDS of one workgroup: the two clusters of
+ * EVERY EDGE have at most CSE_SCHUR_MAX_CLUSTER_CAMERAS cameras together (a
+ * cluster without an edge may have that many alone).
+ *
+ * Host pointer: edges[e] = (g, h), cluster labels of the partition that
+ * cse_schur_set_clusters installed.  num_edges = 0 is legal (every path is
+ * one cluster).  Builds and uploads the filtered plan when the forest changed.
+ * A changed partition DROPS the forest; a changed partition or forest
+ * deactivates a factor that cse_schur_cluster_tridiagonal built.
+ * cse_schur_cluster_jacobi's plan and results do not depend on the forest.
+ * CSE_ERR_INVALID: NULL edges with num_edges > 0, a label out of range, g = h,
+ * an edge given twice (in either orientation), no partition.
+ * CSE_ERR_UNSUPPORTED (the message names the cluster or edge): a cluster with
+ * three edges, a cycle, an edge whose clusters hold more than
+ * CSE_SCHUR_MAX_CLUSTER_CAMERAS cameras together; and cse_schur_set_clusters'
+ * own: held cameras, cse_create_multi, a program that is not Schur-eligible. */
+int cse_schur_set_cluster_forest(cse_evaluator* ev, const int32_t* edges /* [num_edges][2], host */,
+                                 int32_t num_edges);
+
+/* Needs cse_schur_init (any preconditioner), cse_schur_set_clusters and
+ * cse_schur_set_cluster_forest.  Forms M's cells (each with the bits
+ * cse_schur_complement gives it), factors every path and makes the factor the
+ * active preconditioner of cse_schur_precondition and cse_schur_solve
+ * (implicit operator and d_S_values) until the next cse_schur_init or cluster
+ * build.  Asynchronous on the evaluator's stream, no atomics, bit-identical
+ * run to run.
+ * M need not be positive definite.  As the reference does, the factor is tried
+ * on M as it is; if any pivot is not positive, EVERY off-diagonal block M_gh,
+ * of every path, is multiplied by 0.5 and all paths are factored again -- on
+ * the device, without a host wait.  d_scaled (device, may be NULL) receives 0
+ * or 1: whether that second pass ran.  A pivot that is not positive in the
+ * second pass too leaves that path's apply adding zeros and makes the next
+ * cse_wait return CSE_ERR_INVALID.
+ * d_matrices (device, may be NULL) receives the UNSCALED, UNFACTORED cells:
+ * first the cluster matrices exactly as cse_schur_cluster_jacobi lays them
+ * out, then per edge, in the order and orientation cse_schur_set_cluster_forest
+ * received them, S[g, h] dense row-major (9 n_g) x (9 n_h), cameras ascending
+ * inside each cluster. */
+int cse_schur_cluster_tridiagonal(cse_evaluator* ev, double* d_matrices /* may be NULL */,
+                                  int32_t* d_scaled /* may be NULL */);
+
 /* ImplicitSchurComplement::BackSubstitute(x, y) (:216-238): y
  * (num_effective_parameters) = [(E^T E + D_e^2)^-1 E^T (b - F x); x]. */
 int cse_schur_back_substitute(cse_evaluator* ev, const double* d_x, double* d_y);
