@@ -66,6 +66,9 @@ SCHUR_MAX_CLUSTER_CAMERAS = 16  # CSE_SCHUR_MAX_CLUSTER_CAMERAS
 # cse_cgnr_preconditioner
 CGNR_IDENTITY = 0
 CGNR_JACOBI = 1
+# cse_dense_cholesky_factorize's precision
+DENSE_CHOLESKY_FP64 = 0
+DENSE_CHOLESKY_FP32 = 1
 
 # cse_cg_termination (= LinearSolverTerminationType) and cse_cg_reason
 CG_SUCCESS = 0
@@ -225,6 +228,10 @@ SIGNATURES = {
     "cse_cgnr_precondition": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cse_cgnr_solve": (C.c_int, [C.c_void_p, C.POINTER(cse_cg_options), C.c_void_p, C.c_void_p,
                                  C.POINTER(cse_cg_summary)]),
+    "cse_dense_cholesky_factorize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]),
+    "cse_dense_cholesky_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "cse_dense_cholesky_info": (C.c_int, [C.c_void_p, P_i32]),
+    "cse_dense_cholesky_workspace": (C.c_int, [C.c_int64, C.c_int32, P_i64]),
     "cse_create_multi": (C.c_int, [C.POINTER(cse_problem_desc), C.POINTER(cse_options),
                                    P_i32, C.c_int32, C.POINTER(C.c_void_p)]),
     "cse_shard_info": (C.c_int, [C.c_void_p, P_i32, P_i64, P_i32]),

@@ -9,7 +9,10 @@ preconditioned CG on the device's implicit Schur complement
 jacobi / schur_jacobi / identity preconditioners) or on the normal equations
 (--linear_solver cgnr), or -- DENSE_SCHUR, for up to a few hundred cameras --
 the explicit dense Schur complement formed on the device and its Cholesky
-factorization (--linear_solver dense_schur); no Jacobian value leaves HBM.  Prints a FullReport-style table of the evaluator timers
+factorization (--linear_solver dense_schur; --dense_linear_algebra_library cse
+factors S with the library's own Cholesky, in FP64 or, with
+--mixed_precision_solves, in FP32 with FP64 refinement, where the default is
+torch's); no Jacobian value leaves HBM.  Prints a FullReport-style table of the evaluator timers
 (solver.cc: "Residual only evaluation", "Jacobian & residual evaluation",
 "Linear solver", "Plus").
 
@@ -66,6 +69,17 @@ def parse(argv=None):
     ap.add_argument("--max_schur_gb", type=float, default=16.0,
                     help="dense_schur: refuse when the plan and the dense S together take more; "
                          "--use_explicit_schur_complement: the plan, the structure and the blocks of S")
+    ap.add_argument("--dense_linear_algebra_library", default="torch", choices=["torch", "cse"],
+                    help="dense_schur: what factors S.  torch: torch.linalg.cholesky_ex; cse: the "
+                         "library's own factorization (cse_dense_cholesky_factorize, "
+                         "Solver::Options::dense_linear_algebra_library_type = CUDA), no host copy "
+                         "of S or of the step")
+    ap.add_argument("--mixed_precision_solves", action="store_true",
+                    help="with --dense_linear_algebra_library cse: factor a float copy of S and refine "
+                         "in FP64 (Solver::Options::use_mixed_precision_solves)")
+    ap.add_argument("--max_num_refinement_iterations", type=int, default=0,
+                    help="refinement steps of a mixed precision solve "
+                         "(Solver::Options::max_num_refinement_iterations)")
     ap.add_argument("--use_explicit_schur_complement", action="store_true",
                     help="iterative_schur only (bundle_adjuster.cc's flag, Solver::Options::"
                          "use_explicit_schur_complement): form the block-sparse S once per linear solve "
@@ -159,6 +173,16 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.held_cameras < 0:
         raise SystemExit("--held_cameras must not be negative")
+    if args.dense_linear_algebra_library == "cse" and args.linear_solver != "dense_schur":
+        raise SystemExit(f"--dense_linear_algebra_library cse needs --linear_solver dense_schur, not "
+                         f"{args.linear_solver}")
+    if args.mixed_precision_solves and args.dense_linear_algebra_library != "cse":
+        raise SystemExit("--mixed_precision_solves needs --dense_linear_algebra_library cse")
+    if args.max_num_refinement_iterations < 0:
+        raise SystemExit("--max_num_refinement_iterations must not be negative")
+    if args.max_num_refinement_iterations and not args.mixed_precision_solves:
+        raise SystemExit("--max_num_refinement_iterations needs --mixed_precision_solves (and "
+                         "--dense_linear_algebra_library cse)")
     if args.held_cameras and args.linear_solver == "dense_schur":
         raise SystemExit("--held_cameras needs --linear_solver iterative_schur or cgnr, not dense_schur "
                          "(the explicit Schur complement does not take held cameras)")
@@ -413,6 +437,11 @@ def solve(args, stats=None):
     if args.linear_solver == "dense_schur":
         _, _, plan_bytes = ev.schur_complement_plan()
         need = plan_bytes + 8 * f_cols * f_cols
+        dense_precision = (ca._cse.DENSE_CHOLESKY_FP32 if args.mixed_precision_solves
+                           else ca._cse.DENSE_CHOLESKY_FP64)
+        if args.dense_linear_algebra_library == "cse":
+            # The factorization's workspace: in FP32 mode the float copy of S.
+            need += ca.Evaluator.dense_cholesky_workspace(f_cols, dense_precision)
         if need > args.max_schur_gb * 2 ** 30:
             raise SystemExit(f"dense_schur: the plan and the {f_cols} x {f_cols} S take "
                              f"{need / 2 ** 30:.2f} GiB, above --max_schur_gb {args.max_schur_gb:g}; "
@@ -532,6 +561,17 @@ def solve(args, stats=None):
         check_cluster_factor()
         return dx, it
 
+    def cse_cholesky_solve():
+        # DenseCholesky::FactorAndSolve on the device: S stays where
+        # cse_schur_complement wrote it, the step comes back in a device buffer.
+        ev.dense_cholesky_factorize_device(S.data_ptr(), f_cols, precision=dense_precision)
+        xf = torch.empty(f_cols, dtype=f64, device=dev)
+        ev.dense_cholesky_solve_device(rhs.data_ptr(), xf.data_ptr(), args.max_num_refinement_iterations)
+        info = ev.dense_cholesky_info()
+        if info != 0:
+            raise SystemExit(f"dense_schur: S is not positive definite (leading minor {info})")
+        return xf
+
     def dense_schur_solve(lam):
         # DenseSchurComplementSolver (schur_complement_solver.cc): the same
         # augmented system reduced to the dense S by SchurEliminator::Eliminate
@@ -541,7 +581,10 @@ def solve(args, stats=None):
         ev.schur_init_gradient_device(jac.data_ptr(), sqrt_lam_d.data_ptr(), neg_r.data_ptr(),
                                       rhs.data_ptr(), g.data_ptr(), ca._cse.SCHUR_IDENTITY)
         ev.schur_complement_device(S.data_ptr())
-        xf = cholesky_solve(S, rhs)
+        if args.dense_linear_algebra_library == "cse":
+            xf = timed("Dense Cholesky factor & solve", cse_cholesky_solve)
+        else:
+            xf = cholesky_solve(S, rhs)
         dx = torch.empty(n, dtype=f64, device=dev)
         ev.schur_back_substitute_device(xf.data_ptr(), dx.data_ptr())
         return dx, 0

@@ -828,6 +828,47 @@ class Evaluator:
         return _cse.check(_cse.lib().cse_schur_complement(self.handle, d_S, int(ld)),
                           "cse_schur_complement")
 
+    def dense_cholesky_factorize_device(self, d_A, n, ld=None, precision=_cse.DENSE_CHOLESKY_FP64):
+        """Cholesky factorization of the row-major n x n matrix at d_A (leading
+        dimension ld, default n), read from its lower triangle alone
+        (cse_dense_cholesky_factorize).  DENSE_CHOLESKY_FP64: in place, the lower
+        triangle receives L.  DENSE_CHOLESKY_FP32: d_A is not written, a float
+        copy is factored in the evaluator's workspace.  Either way d_A must
+        stay as it is until the last solve.  Asynchronous; a pivot that is not
+        positive shows in dense_cholesky_info()."""
+        if ld is None:
+            ld = n
+        return _cse.check(_cse.lib().cse_dense_cholesky_factorize(self.handle, int(n), d_A, int(ld),
+                                                                  int(precision)),
+                          "cse_dense_cholesky_factorize")
+
+    def dense_cholesky_solve_device(self, d_rhs, d_x, max_num_refinement_iterations=0):
+        """x = A^-1 rhs from the last factorization (cse_dense_cholesky_solve);
+        d_rhs and d_x may be the same buffer.  With an FP32 factor,
+        max_num_refinement_iterations FP64 refinement steps follow the first
+        solve; with an FP64 factor it must be 0.  Zeros after a failed
+        factorization."""
+        return _cse.check(_cse.lib().cse_dense_cholesky_solve(self.handle, d_rhs, d_x,
+                                                              int(max_num_refinement_iterations)),
+                          "cse_dense_cholesky_solve")
+
+    def dense_cholesky_info(self):
+        """Waits for the stream; 0, or the 1-based order of the first leading
+        minor that is not positive definite (cse_dense_cholesky_info)."""
+        info = C.c_int32()
+        _cse.check(_cse.lib().cse_dense_cholesky_info(self.handle, C.byref(info)),
+                   "cse_dense_cholesky_info")
+        return info.value
+
+    @staticmethod
+    def dense_cholesky_workspace(n, precision):
+        """The device bytes a factorization of this n and precision holds
+        (cse_dense_cholesky_workspace); allocates nothing."""
+        nbytes = C.c_int64()
+        _cse.check(_cse.lib().cse_dense_cholesky_workspace(int(n), int(precision), C.byref(nbytes)),
+                   "cse_dense_cholesky_workspace")
+        return nbytes.value
+
     def schur_complement_plan(self):
         """(num_blocks, num_pairs, plan_bytes) of schur_complement_device's
         co-visibility plan: the non-zero 9 x 9 blocks of S's upper triangle,

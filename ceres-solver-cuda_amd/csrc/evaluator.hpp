@@ -328,6 +328,16 @@ struct cse_evaluator {
     int preconditioner = CSE_CGNR_IDENTITY;
     const double *jac = nullptr, *D = nullptr;
   } cgnr;
+  // The dense Cholesky factorization (cse_dense_cholesky_*, dense_cholesky.hip):
+  // the workspace cse::PlanDenseCholesky lays out, kept and grown across
+  // calls, and what the last factorize bound.
+  struct DenseCholesky {
+    cse::DevBuf<unsigned char> workspace;
+    cse::DenseCholeskyPlan plan;
+    bool factored = false;
+    double* A = nullptr;  // the caller's matrix: L in FP64, read by a refining solve in FP32
+    int64_t ld = 0;
+  } dense;
 };
 
 namespace cse {

@@ -1565,4 +1565,40 @@ int PlanSchurTridiagonal(const int32_t* ids, int64_t n, int32_t first_id, int64_
   return CSE_OK;
 }
 
+int PlanDenseCholesky(int64_t n, int32_t precision, DenseCholeskyPlan* plan) {
+  if (!plan) return CseFail(CSE_ERR_INVALID, "dense Cholesky plan: null plan");
+  if (n < 1) return CseFail(CSE_ERR_INVALID, "dense Cholesky: n must be at least 1");
+  if (precision != CSE_DENSE_CHOLESKY_FP64 && precision != CSE_DENSE_CHOLESKY_FP32)
+    return CseFail(CSE_ERR_INVALID, "dense Cholesky: unknown precision " + std::to_string(precision));
+  DenseCholeskyPlan P;
+  P.n = n;
+  P.precision = precision;
+  P.num_panels = (n + kDenseCholeskyNB - 1) / kDenseCholeskyNB;
+  P.padded = P.num_panels * kDenseCholeskyNB;
+  const bool f32 = precision == CSE_DENSE_CHOLESKY_FP32;
+  // Diagonal, panel and trailing update per step; the last step has no rows below.
+  P.factor_launches = 3 * P.num_panels - 2 + (f32 ? 1 : 0);
+  P.substitution_launches = 2 * P.num_panels;
+  const int64_t elem = f32 ? 4 : 8;
+  auto segment = [](int64_t bytes) { return (bytes + kDenseCholeskyAlign - 1) / kDenseCholeskyAlign * kDenseCholeskyAlign; };
+  int64_t off = 0;
+  P.matrix_off = off;
+  if (f32) off += segment(n * n * elem);
+  P.inverse_off = off;
+  off += segment(P.num_panels * kDenseCholeskyNB * kDenseCholeskyNB * elem);
+  P.v_off = off;
+  off += segment(P.padded * elem);
+  P.y_off = off;
+  off += segment(P.padded * elem);
+  P.x_off = off;
+  if (f32) off += segment(P.padded * 8);
+  P.r_off = off;
+  if (f32) off += segment(P.padded * 8);
+  P.flag_off = off;
+  off += kDenseCholeskyAlign;
+  P.workspace_bytes = off;
+  *plan = P;
+  return CSE_OK;
+}
+
 }  // namespace cse

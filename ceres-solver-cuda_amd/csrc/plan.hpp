@@ -489,6 +489,57 @@ struct SchurSparsePlan : SchurSparseCounts {
 int PlanSchurSparse(const int32_t* ids, int64_t n, const SchurPairPlan& plan, int32_t first_id, int64_t C,
                     bool counts_only, SchurSparsePlan* sparse);
 
+// ---- The dense Cholesky factorization (cse_dense_cholesky_*): a blocked
+// right-looking factorization, one panel of kDenseCholeskyNB columns per step.
+// Step k launches the diagonal kernel (one workgroup), then -- unless it is
+// the last -- the panel kernel over the block rows below it and the trailing
+// update over the lower-triangle tiles of the remaining block rows; a solve
+// launches one kernel per block row forward and one backward.
+constexpr int kDenseCholeskyNB = 64;
+constexpr int64_t kDenseCholeskyAlign = 256;  // every workspace segment's size is a multiple
+
+struct DenseCholeskyPlan {
+  int64_t n = 0;
+  int32_t precision = 0;
+  int64_t num_panels = 0;  // ceil(n / NB)
+  int64_t padded = 0;      // num_panels * NB: the length of the workspace vectors
+  // Kernel launches of a factorization (the FP32 cast included), of one
+  // forward + backward substitution, and of a whole solve with `refinements`
+  // refinement iterations: SolveLaunches(refinements).
+  int64_t factor_launches = 0, substitution_launches = 0;
+  // The workspace, in bytes from its start.  FP64: the inverses of the
+  // diagonal blocks [num_panels][NB][NB], the vectors v and y [padded], the
+  // failure flag.  FP32: the float copy of the matrix [n][n] first, those in
+  // float, and the FP64 vectors x and r [padded] of the refinement.
+  int64_t matrix_off = 0, inverse_off = 0, v_off = 0, y_off = 0, x_off = 0, r_off = 0, flag_off = 0;
+  int64_t workspace_bytes = 0;
+  int64_t SolveLaunches(int64_t refinements) const {
+    // FP64: load, substitutions, store.  FP32: init, per iteration cast +
+    // substitutions + accumulate, a residual between iterations, store.
+    if (precision == 0) return substitution_launches + 2;
+    return 1 + (refinements + 1) * (substitution_launches + 2) + refinements + 1;
+  }
+};
+
+// The launch grids of step k (workgroups): the panel kernel takes the block
+// rows k+1 .. num_panels-1, the trailing update the lower-triangle tiles (i, j),
+// k < j <= i, of those R rows, folded into (R + 1) x ceil(R / 2) workgroups:
+// grid row y holds block row y's y + 1 tiles and then block row R-1-y's R - y.
+constexpr int64_t DenseCholeskyRowsBelow(int64_t num_panels, int64_t k) { return num_panels - k - 1; }
+constexpr int64_t DenseCholeskyTrailingGridX(int64_t R) { return R + 1; }
+constexpr int64_t DenseCholeskyTrailingGridY(int64_t R) { return (R + 1) / 2; }
+struct DenseCholeskyTile {
+  int64_t i, j;  // block row and column among the R remaining, j <= i
+  bool live;     // false: the odd middle row's second half, no tile
+};
+constexpr DenseCholeskyTile DenseCholeskyTrailingTile(int64_t R, int64_t x, int64_t y) {
+  if (x <= y) return DenseCholeskyTile{y, x, true};
+  return DenseCholeskyTile{R - 1 - y, x - y - 1, R - 1 - y != y};
+}
+
+// CSE_ERR_INVALID: n < 1 or an unknown precision.
+int PlanDenseCholesky(int64_t n, int32_t precision, DenseCholeskyPlan* plan);
+
 }  // namespace cse
 
 #endif  // CSE_PLAN_HPP_

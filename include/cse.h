@@ -895,6 +895,71 @@ int cse_cgnr_precondition(cse_evaluator* ev, const double* d_x, double* d_y);
 int cse_cgnr_solve(cse_evaluator* ev, const cse_cg_options* options, const double* d_rhs,
                    double* d_x, cse_cg_summary* summary);
 
+/* ---- Dense Cholesky on the device ----------------------------------------
+ * DenseCholesky's device forms (internal/ceres/dense_cholesky.h:195-302,
+ * dense_cholesky.cc:348-640): CUDADenseCholesky, an FP64 potrf/potrs, and
+ * CUDADenseCholeskyMixedPrecision, an FP32 factor with FP64 iterative
+ * refinement; what Solver::Options::dense_linear_algebra_library_type = CUDA,
+ * use_mixed_precision_solves and max_num_refinement_iterations select.  No
+ * vendor library: a blocked right-looking factorization in HIP, 64 columns per
+ * panel, the trailing update on the matrix cores.  The evaluator supplies the
+ * device and the stream and owns the workspace; nothing here needs a
+ * Schur-eligible program, and n is the caller's.  Everything is asynchronous
+ * on the evaluator's stream (no host wait in factorize or solve), uses no
+ * atomics and is bit-identical from run to run.  CSE_ERR_UNSUPPORTED on a
+ * cse_create_multi handle. */
+enum { CSE_DENSE_CHOLESKY_FP64 = 0, CSE_DENSE_CHOLESKY_FP32 = 1 };
+
+/* DenseCholesky::Factorize (dense_cholesky.h:67-75; CUDADenseCholesky::Factorize
+ * dense_cholesky.cc:364-407, CUDADenseCholeskyMixedPrecision::Factorize
+ * :543-560).  d_A: row-major n x n, leading dimension ld >= n, symmetric
+ * positive definite; only the lower triangle, diagonal included, is ever read
+ * (dense_cholesky.h:67-69); the strict upper triangle and the entries
+ * [row][n..ld) are neither read nor written.  cse_schur_complement's output is
+ * a valid input as it stands.
+ *   CSE_DENSE_CHOLESKY_FP64: in place, the lower triangle of d_A receives L
+ *     (A = L L^T); d_A must stay valid and unmodified until the last solve.
+ *   CSE_DENSE_CHOLESKY_FP32: d_A is not written; its lower triangle is cast to
+ *     float into the workspace and factored there in single precision (the
+ *     reference's Spotrf).  A refining solve reads d_A again, so it must stay
+ *     unchanged until the last solve (bound as cse_schur_init binds the
+ *     Jacobian).
+ * A pivot that is not positive and finite stops the factorization's effect
+ * (the panels before it are done: in FP64 d_A's lower triangle is then
+ * unspecified, partly L and partly updated, as after LAPACK's potrf)
+ * (LAPACK's info > 0, LinearSolverTerminationType::FAILURE at
+ * dense_cholesky.cc:397-403): cse_dense_cholesky_info reports it, the
+ * evaluator's status word and cse_wait are not affected.  CSE_ERR_INVALID: a
+ * null pointer, n < 1, ld < n, an unknown precision.  CSE_ERR_OOM: the
+ * workspace (cse_dense_cholesky_workspace) does not fit; it is kept across
+ * calls, grown when needed and released by cse_destroy. */
+int cse_dense_cholesky_factorize(cse_evaluator* ev, int64_t n, double* d_A, int64_t ld, int32_t precision);
+
+/* DenseCholesky::Solve (CUDADenseCholesky::Solve dense_cholesky.cc:409-450:
+ * x = L^-T L^-1 rhs; CUDADenseCholeskyMixedPrecision::Solve :594-637, statement
+ * for statement: x = 0, r = rhs; for i = 0 .. max_num_refinement_iterations:
+ * r32 = (float) r, c = L32^-T L32^-1 r32 in FP32, x += (double) c; and, if
+ * i < max, r = rhs - A x in FP64 from the lower triangle of d_A).  d_rhs, d_x:
+ * n entries, the same buffer or disjoint.  After a failed factorization d_x is
+ * assigned zeros.  CSE_ERR_INVALID: a null pointer, a negative refinement
+ * count, no prior factorize, d_x overlapping d_rhs partially.
+ * CSE_ERR_UNSUPPORTED: FP64 with a refinement count other than 0 (the factor
+ * has overwritten the matrix a residual would need; RefinedDenseCholesky is
+ * not provided). */
+int cse_dense_cholesky_solve(cse_evaluator* ev, const double* d_rhs, double* d_x,
+                             int32_t max_num_refinement_iterations);
+
+/* potrf's info (dense_cholesky.cc:386-403): waits on the stream; 0 after a
+ * success, else the 1-based order of the first leading minor that is not
+ * positive definite.  A later factorize starts again from 0.  CSE_ERR_INVALID
+ * before any factorize. */
+int cse_dense_cholesky_info(cse_evaluator* ev, int32_t* info);
+
+/* The device bytes a factorize of this n and precision holds (potrf's
+ * bufferSize query, dense_cholesky.cc:372-383, plus the float copy and the
+ * refinement vectors of :543-592); allocates nothing, needs no evaluator. */
+int cse_dense_cholesky_workspace(int64_t n, int32_t precision, int64_t* device_bytes);
+
 /* ---- One host solve, several GPUs --------------------------------------
  * The reference evaluates on one device (ContextImpl's single stream,
  * include/ceres/internal/cuda_buffer.h:98) and Ceres' host solve calls one
