@@ -69,6 +69,10 @@ CGNR_JACOBI = 1
 # cse_dense_cholesky_factorize's precision
 DENSE_CHOLESKY_FP64 = 0
 DENSE_CHOLESKY_FP32 = 1
+# cse_sparse_cholesky_analyze's ordering
+SPARSE_ORDERING_NATURAL = 0
+SPARSE_ORDERING_MINIMUM_DEGREE = 1
+SPARSE_ORDERING_GIVEN = 2
 
 # cse_cg_termination (= LinearSolverTerminationType) and cse_cg_reason
 CG_SUCCESS = 0
@@ -176,6 +180,12 @@ class cse_spse_summary(C.Structure):
                 ("norm_first", C.c_double), ("norm_last", C.c_double)]
 
 
+class cse_sparse_cholesky_summary(C.Structure):
+    _fields_ = [("num_block_rows", C.c_int64), ("num_input_blocks", C.c_int64),
+                ("num_factor_blocks", C.c_int64), ("num_block_products", C.c_int64),
+                ("device_bytes", C.c_int64), ("num_levels", C.c_int32), ("max_level_columns", C.c_int32)]
+
+
 P_i32 = C.POINTER(C.c_int32)
 P_i64 = C.POINTER(C.c_int64)
 P_f64 = C.POINTER(C.c_double)
@@ -232,6 +242,13 @@ SIGNATURES = {
     "cse_dense_cholesky_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "cse_dense_cholesky_info": (C.c_int, [C.c_void_p, P_i32]),
     "cse_dense_cholesky_workspace": (C.c_int, [C.c_int64, C.c_int32, P_i64]),
+    "cse_sparse_cholesky_analyze": (C.c_int, [C.c_void_p, C.c_int64, P_i64, P_i32, C.c_int32, P_i32,
+                                              C.POINTER(cse_sparse_cholesky_summary)]),
+    "cse_sparse_cholesky_structure": (C.c_int, [C.c_void_p, P_i32, P_i64, P_i32, P_i32, P_i32]),
+    "cse_sparse_cholesky_factorize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cse_sparse_cholesky_factor_values": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cse_sparse_cholesky_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "cse_sparse_cholesky_info": (C.c_int, [C.c_void_p, P_i32]),
     "cse_create_multi": (C.c_int, [C.POINTER(cse_problem_desc), C.POINTER(cse_options),
                                    P_i32, C.c_int32, C.POINTER(C.c_void_p)]),
     "cse_shard_info": (C.c_int, [C.c_void_p, P_i32, P_i64, P_i32]),

@@ -61,11 +61,19 @@ def parse(argv=None):
     ap.add_argument("--max_linear_solver_iterations", type=int, default=500)
     ap.add_argument("--eta", type=float, default=1e-2, help="CG forcing tolerance")
     ap.add_argument("--initial_trust_region_radius", type=float, default=1e4)
-    ap.add_argument("--linear_solver", default="iterative_schur", choices=["iterative_schur", "cgnr", "dense_schur"],
+    ap.add_argument("--linear_solver", default="iterative_schur",
+                    choices=["iterative_schur", "cgnr", "dense_schur", "sparse_schur"],
                     help="iterative_schur (the reference benchmark's, README.md:143-184): PCG on "
                          "the implicit Schur complement (cse_schur_*); cgnr: PCG on the normal "
                          "equations (cse_cgnr_multiply); dense_schur: the dense reduced camera "
-                         "matrix (cse_schur_complement) and its Cholesky factorization")
+                         "matrix (cse_schur_complement) and its Cholesky factorization; "
+                         "sparse_schur: the block-sparse reduced camera matrix "
+                         "(cse_schur_complement_sparse) and its block-sparse Cholesky "
+                         "factorization (cse_sparse_cholesky_*), analysed once per run")
+    ap.add_argument("--sparse_ordering", default="minimum_degree", choices=["minimum_degree", "natural"],
+                    help="sparse_schur: the elimination order of the cameras "
+                         "(Solver::Options::linear_solver_ordering_type; minimum_degree is the library's "
+                         "greedy rule, not SuiteSparse's AMD)")
     ap.add_argument("--max_schur_gb", type=float, default=16.0,
                     help="dense_schur: refuse when the plan and the dense S together take more; "
                          "--use_explicit_schur_complement: the plan, the structure and the blocks of S")
@@ -180,7 +188,21 @@ def parse(argv=None):
         raise SystemExit("--mixed_precision_solves needs --dense_linear_algebra_library cse")
     if args.max_num_refinement_iterations < 0:
         raise SystemExit("--max_num_refinement_iterations must not be negative")
-    if args.max_num_refinement_iterations and not args.mixed_precision_solves:
+    if args.linear_solver == "sparse_schur":
+        # What sparse_schur does not take, one message each (--dense_linear_algebra_library
+        # cse and --mixed_precision_solves have met theirs above).
+        if args.held_cameras:
+            raise SystemExit("--held_cameras needs --linear_solver iterative_schur or cgnr, not sparse_schur "
+                             "(the explicit Schur complement does not take held cameras)")
+        for flag, given in (("--use_explicit_schur_complement", args.use_explicit_schur_complement),
+                            ("--preconditioner " + args.preconditioner, args.preconditioner != "jacobi"),
+                            ("--use_spse_initialization", args.use_spse_initialization),
+                            ("--device_pcg", args.device_pcg),
+                            ("--pcg_termination quadratic", args.pcg_termination == "quadratic")):
+            if given:
+                raise SystemExit(f"{flag} needs --linear_solver iterative_schur, not sparse_schur")
+    if (args.max_num_refinement_iterations and not args.mixed_precision_solves
+            and args.linear_solver != "sparse_schur"):
         raise SystemExit("--max_num_refinement_iterations needs --mixed_precision_solves (and "
                          "--dense_linear_algebra_library cse)")
     if args.held_cameras and args.linear_solver == "dense_schur":
@@ -447,6 +469,31 @@ def solve(args, stats=None):
                              f"{need / 2 ** 30:.2f} GiB, above --max_schur_gb {args.max_schur_gb:g}; "
                              "use iterative_schur")
         S = torch.empty((f_cols, f_cols), dtype=f64, device=dev)
+    if args.linear_solver == "sparse_schur":
+        # SparseSchurComplementSolver: InitStorage's block structure, then the
+        # SparseCholesky's symbolic analysis, both once per run
+        # (sparse_cholesky.h:55-56).
+        _, _, plan_bytes = ev.schur_complement_plan()
+        t0 = time.perf_counter()
+        s_row_begin, s_block_col, structure_bytes = ev.schur_complement_sparse_structure()
+        timers.add("Schur complement structure", time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        sparse_summary = ev.sparse_cholesky_analyze(
+            s_row_begin, s_block_col,
+            {"minimum_degree": ca._cse.SPARSE_ORDERING_MINIMUM_DEGREE,
+             "natural": ca._cse.SPARSE_ORDERING_NATURAL}[args.sparse_ordering])
+        timers.add("Sparse Cholesky analysis", time.perf_counter() - t0)
+        print(f"sparse_schur: {sparse_summary.num_input_blocks} blocks of S, {sparse_summary.num_factor_blocks} "
+              f"of L ({args.sparse_ordering}), {sparse_summary.num_block_products} block products, "
+              f"{sparse_summary.num_levels} levels of at most {sparse_summary.max_level_columns} columns")
+        if stats is not None:
+            stats["sparse_cholesky"] = sparse_summary
+        need = structure_bytes + plan_bytes + 648 * len(s_block_col) + sparse_summary.device_bytes
+        if need > args.max_schur_gb * 2 ** 30:
+            raise SystemExit(f"sparse_schur: the plan, the blocks of S and its factor take "
+                             f"{need / 2 ** 30:.2f} GiB, above --max_schur_gb {args.max_schur_gb:g}; "
+                             "use iterative_schur")
+        S_values = torch.empty(81 * len(s_block_col), dtype=f64, device=dev)
     if args.use_explicit_schur_complement:
         _, _, plan_bytes = ev.schur_complement_plan()
         _, num_blocks, structure_bytes = ev.schur_complement_sparse_counts()
@@ -589,6 +636,36 @@ def solve(args, stats=None):
         ev.schur_back_substitute_device(xf.data_ptr(), dx.data_ptr())
         return dx, 0
 
+    def sparse_cholesky_solve():
+        # SparseCholesky::FactorAndSolve on the device: the blocks stay where
+        # cse_schur_complement_sparse wrote them, the step comes back in a
+        # device buffer.
+        ev.sparse_cholesky_factorize_device(S_values.data_ptr())
+        xf = torch.empty(f_cols, dtype=f64, device=dev)
+        ev.sparse_cholesky_solve_device(rhs.data_ptr(), xf.data_ptr(), args.max_num_refinement_iterations)
+        return xf, ev.sparse_cholesky_info()
+
+    def sparse_schur_solve(lam):
+        # SparseSchurComplementSolver (schur_complement_solver.cc:290-333): the
+        # same augmented system reduced to the block-sparse S, S dx_f = rhs by
+        # the block-sparse Cholesky factorization, back substitution; one
+        # "iteration" (:329).
+        torch.neg(r, out=neg_r)
+        sqrt_lam_d = torch.sqrt(lam * D)
+        ev.schur_init_gradient_device(jac.data_ptr(), sqrt_lam_d.data_ptr(), neg_r.data_ptr(),
+                                      rhs.data_ptr(), g.data_ptr(), ca._cse.SCHUR_IDENTITY)
+        ev.schur_complement_sparse_device(S_values.data_ptr())
+        xf, info = timed("Sparse Cholesky factor & solve", sparse_cholesky_solve)
+        if info != 0:
+            # LinearSolverTerminationType::FAILURE (schur_complement_solver.cc:
+            # 316-321): no step; the zero step is rejected and the radius shrinks.
+            print(f"sparse_schur: S is not positive definite (permuted scalar column {info - 1}); "
+                  "the step is rejected")
+            return torch.zeros(n, dtype=f64, device=dev), 1
+        dx = torch.empty(n, dtype=f64, device=dev)
+        ev.schur_back_substitute_device(xf.data_ptr(), dx.data_ptr())
+        return dx, 1
+
     # Solver::Options::jacobi_scaling (trust_region_minimizer.cc:259-275): the
     # scaling comes from the first Jacobian and every Jacobian is scaled in
     # place; the solvers, the LM diagonal and the model then live in the scaled
@@ -648,6 +725,7 @@ def solve(args, stats=None):
             D.clamp_(min=1e-6)
             d_stale = False
         solver = {"iterative_schur": schur_solve, "dense_schur": dense_schur_solve,
+                  "sparse_schur": sparse_schur_solve,
                   "cgnr": cgnr_device if args.device_cgnr else cgnr}[args.linear_solver]
         dx, cg_iters = timed("Linear solver", lambda: solver(1.0 / radius))
         # dx is the step of the (scaled) linear system; Plus takes delta =

@@ -569,6 +569,7 @@ class Evaluator:
             _cse.check(L.cse_create_multi(C.byref(self.desc), C.byref(opts), devs, len(devices),
                                           C.byref(h)), "cse_create_multi")
         self.handle = h
+        self._sparse_cholesky_summary = None  # of the last sparse_cholesky_analyze
 
     def close(self):
         if getattr(self, "handle", None):
@@ -868,6 +869,85 @@ class Evaluator:
         _cse.check(_cse.lib().cse_dense_cholesky_workspace(int(n), int(precision), C.byref(nbytes)),
                    "cse_dense_cholesky_workspace")
         return nbytes.value
+
+    def sparse_cholesky_analyze(self, row_begin, block_col, ordering=_cse.SPARSE_ORDERING_MINIMUM_DEGREE,
+                                permutation=None):
+        """The symbolic analysis of a block-sparse Cholesky factorization
+        (cse_sparse_cholesky_analyze): the upper triangle of a symmetric matrix
+        of 9 x 9 blocks as schur_complement_sparse_structure returns it (host
+        arrays, every row's diagonal block first, columns ascending).
+        ordering: _cse.SPARSE_ORDERING_NATURAL, _MINIMUM_DEGREE or _GIVEN with
+        permutation[k] = the original block row at position k.  Once per
+        structure; returns the _cse.cse_sparse_cholesky_summary."""
+        row_begin = np.ascontiguousarray(row_begin, np.int64)
+        block_col = np.ascontiguousarray(block_col, np.int32)
+        perm = None
+        if permutation is not None:
+            perm = np.ascontiguousarray(permutation, np.int32)
+        summary = _cse.cse_sparse_cholesky_summary()
+        _cse.check(_cse.lib().cse_sparse_cholesky_analyze(
+            self.handle, len(row_begin) - 1, row_begin.ctypes.data_as(_cse.P_i64),
+            block_col.ctypes.data_as(_cse.P_i32), int(ordering),
+            None if perm is None else perm.ctypes.data_as(_cse.P_i32), C.byref(summary)),
+            "cse_sparse_cholesky_analyze")
+        self._sparse_cholesky_summary = summary
+        return summary
+
+    def sparse_cholesky_structure(self):
+        """(permutation int32[N], factor_row_begin int64[N+1], factor_block_col
+        int32[num_factor_blocks], parent int32[N], level int32[N]) of the last
+        analysis (cse_sparse_cholesky_structure): L's block rows in the
+        permuted order, a row's columns ascending and its diagonal last; the
+        elimination tree's parent (-1 at a root) and each column's level.  The
+        sizes are those of this object's last sparse_cholesky_analyze: an
+        analysis made through the C ABI directly is not seen here."""
+        s = self._sparse_cholesky_summary
+        if s is None:  # the library's own refusal: no analyze before it
+            _cse.check(_cse.lib().cse_sparse_cholesky_structure(self.handle, None, None, None, None, None),
+                       "cse_sparse_cholesky_structure")
+            raise RuntimeError("cse_sparse_cholesky_structure: the analysis was not made by sparse_cholesky_analyze")
+        perm = np.empty(s.num_block_rows, np.int32)
+        row_begin = np.empty(s.num_block_rows + 1, np.int64)
+        block_col = np.empty(s.num_factor_blocks, np.int32)
+        parent = np.empty(s.num_block_rows, np.int32)
+        level = np.empty(s.num_block_rows, np.int32)
+        _cse.check(_cse.lib().cse_sparse_cholesky_structure(
+            self.handle, perm.ctypes.data_as(_cse.P_i32), row_begin.ctypes.data_as(_cse.P_i64),
+            block_col.ctypes.data_as(_cse.P_i32), parent.ctypes.data_as(_cse.P_i32),
+            level.ctypes.data_as(_cse.P_i32)), "cse_sparse_cholesky_structure")
+        return perm, row_begin, block_col, parent, level
+
+    def sparse_cholesky_factorize_device(self, d_values):
+        """The numeric factorization of d_values[num_input_blocks][9][9], laid
+        out as schur_complement_sparse_device writes them, into storage the
+        evaluator owns (cse_sparse_cholesky_factorize).  d_values is read only
+        and must stay as it is until the last refining solve.  Asynchronous; a
+        pivot that is not positive shows in sparse_cholesky_info()."""
+        return _cse.check(_cse.lib().cse_sparse_cholesky_factorize(self.handle, d_values),
+                          "cse_sparse_cholesky_factorize")
+
+    def sparse_cholesky_factor_values_device(self, d_L):
+        """L's values into d_L[num_factor_blocks][9][9], in
+        sparse_cholesky_structure's order (cse_sparse_cholesky_factor_values)."""
+        return _cse.check(_cse.lib().cse_sparse_cholesky_factor_values(self.handle, d_L),
+                          "cse_sparse_cholesky_factor_values")
+
+    def sparse_cholesky_solve_device(self, d_rhs, d_x, max_num_refinement_iterations=0):
+        """x = A^-1 rhs in the original order from the last factorization
+        (cse_sparse_cholesky_solve); d_rhs and d_x may be the same buffer;
+        max_num_refinement_iterations FP64 refinement steps follow the first
+        solve.  Zeros after a failed factorization."""
+        return _cse.check(_cse.lib().cse_sparse_cholesky_solve(self.handle, d_rhs, d_x,
+                                                               int(max_num_refinement_iterations)),
+                          "cse_sparse_cholesky_solve")
+
+    def sparse_cholesky_info(self):
+        """Waits for the stream; 0, or 1 + the smallest permuted scalar column
+        whose pivot failed (cse_sparse_cholesky_info)."""
+        info = C.c_int32()
+        _cse.check(_cse.lib().cse_sparse_cholesky_info(self.handle, C.byref(info)),
+                   "cse_sparse_cholesky_info")
+        return info.value
 
     def schur_complement_plan(self):
         """(num_blocks, num_pairs, plan_bytes) of schur_complement_device's

@@ -338,6 +338,21 @@ struct cse_evaluator {
     double* A = nullptr;  // the caller's matrix: L in FP64, read by a refining solve in FP32
     int64_t ld = 0;
   } dense;
+  // The block-sparse Cholesky factorization (cse_sparse_cholesky_*,
+  // sparse_cholesky.hip): the host plan of the last analyze
+  // (cse::PlanSparseCholesky) and its tables on the device; L, the inverses of
+  // its diagonal blocks, the two solve vectors and the status words, allocated
+  // by the first factorize after an analyze; the values the last factorize bound.
+  struct SparseCholesky {
+    cse::SparseCholeskyPlan plan;
+    bool analyzed = false, factored = false;
+    cse::DevBuf<int32_t> permutation, position, block_col, block_row, col_block, source, level_columns, level_targets;
+    cse::DevBuf<int32_t> in_block_col, in_col_block, in_col_row;
+    cse::DevBuf<int64_t> row_begin, col_begin, in_row_begin, in_col_begin;
+    cse::DevBuf<double> L, inverse, y, x;
+    cse::DevBuf<int> status;  // [N] per column, then info
+    const double* values = nullptr;
+  } sparse;
 };
 
 namespace cse {

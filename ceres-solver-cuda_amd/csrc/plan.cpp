@@ -1601,4 +1601,239 @@ int PlanDenseCholesky(int64_t n, int32_t precision, DenseCholeskyPlan* plan) {
   return CSE_OK;
 }
 
+namespace {
+
+// The input's format (PlanSchurSparse's): diagonal first, columns ascending and in range.
+int ValidateSparseRows(int64_t N, const int64_t* row_begin, const int32_t* block_col) {
+  if (N < 1) return CseFail(CSE_ERR_INVALID, "sparse Cholesky: num_block_rows must be at least 1");
+  if (N > (INT32_MAX - 1) / 9)
+    return CseFail(CSE_ERR_UNSUPPORTED, "sparse Cholesky: 9 num_block_rows + 1 does not fit int32");
+  if (!row_begin || !block_col) return CseFail(CSE_ERR_INVALID, "sparse Cholesky: null pointer");
+  if (row_begin[0] != 0) return CseFail(CSE_ERR_INVALID, "sparse Cholesky: row_begin[0] is not 0");
+  for (int64_t r = 0; r < N; ++r) {
+    const int64_t b = row_begin[r], e = row_begin[r + 1];
+    if (e <= b || block_col[b] != r)
+      return CseFail(CSE_ERR_INVALID,
+                     "sparse Cholesky: block row " + std::to_string(r) + " does not start with its diagonal block");
+    for (int64_t k = b + 1; k < e; ++k)
+      if (block_col[k] <= block_col[k - 1] || block_col[k] >= N)
+        return CseFail(CSE_ERR_INVALID, "sparse Cholesky: block row " + std::to_string(r) +
+                                            " has columns that do not ascend or are out of range");
+    if (e >= INT32_MAX) return CseFail(CSE_ERR_UNSUPPORTED, "sparse Cholesky: 2^31 or more input blocks");
+  }
+  return CSE_OK;
+}
+
+inline int Popcount(const uint64_t* w, int64_t words) {
+  int n = 0;
+  for (int64_t k = 0; k < words; ++k) n += __builtin_popcountll(w[k]);
+  return n;
+}
+
+}  // namespace
+
+int SparseCholeskyMinimumDegree(int64_t N, const int64_t* row_begin, const int32_t* block_col,
+                                std::vector<int32_t>* permutation) {
+  try {
+    const int64_t W = (N + 63) / 64;
+    std::vector<uint64_t> adj((size_t)(N * W), 0);
+    auto set = [&](int64_t a, int64_t b) { adj[(size_t)(a * W + b / 64)] |= uint64_t(1) << (b % 64); };
+    for (int64_t r = 0; r < N; ++r)
+      for (int64_t k = row_begin[r] + 1; k < row_begin[r + 1]; ++k) set(r, block_col[k]), set(block_col[k], r);
+    std::vector<int32_t> degree((size_t)N);
+    std::vector<char> alive((size_t)N, 1);
+    for (int64_t v = 0; v < N; ++v) degree[(size_t)v] = Popcount(&adj[(size_t)(v * W)], W);
+    permutation->clear();
+    permutation->reserve((size_t)N);
+    for (int64_t remaining = N; remaining > 0; --remaining) {
+      int64_t v = -1;
+      for (int64_t u = 0; u < N; ++u)
+        if (alive[(size_t)u] && (v < 0 || degree[(size_t)u] < degree[(size_t)v])) v = u;
+      if (degree[(size_t)v] == remaining - 1) {  // a clique: index order from here
+        for (int64_t u = 0; u < N; ++u)
+          if (alive[(size_t)u]) permutation->push_back((int32_t)u);
+        break;
+      }
+      permutation->push_back((int32_t)v);
+      alive[(size_t)v] = 0;
+      const uint64_t* rv = &adj[(size_t)(v * W)];
+      for (int64_t w = 0; w < W; ++w)
+        for (uint64_t bits = rv[w]; bits; bits &= bits - 1) {
+          const int64_t u = 64 * w + __builtin_ctzll(bits);
+          uint64_t* ru = &adj[(size_t)(u * W)];
+          for (int64_t k = 0; k < W; ++k) ru[k] |= rv[k];
+          ru[u / 64] &= ~(uint64_t(1) << (u % 64));
+          ru[v / 64] &= ~(uint64_t(1) << (v % 64));
+          degree[(size_t)u] = Popcount(ru, W);
+        }
+    }
+  } catch (const std::bad_alloc&) {
+    return CseFail(CSE_ERR_OOM, "sparse Cholesky: host allocation of the minimum-degree bit rows failed");
+  }
+  return CSE_OK;
+}
+
+int PlanSparseCholesky(int64_t N, const int64_t* row_begin, const int32_t* block_col, int32_t ordering,
+                       const int32_t* permutation, SparseCholeskyPlan* plan) {
+  if (!plan) return CseFail(CSE_ERR_INVALID, "sparse Cholesky plan: null plan");
+  int rc = ValidateSparseRows(N, row_begin, block_col);
+  if (rc) return rc;
+  if (ordering != CSE_SPARSE_ORDERING_NATURAL && ordering != CSE_SPARSE_ORDERING_MINIMUM_DEGREE &&
+      ordering != CSE_SPARSE_ORDERING_GIVEN)
+    return CseFail(CSE_ERR_INVALID, "sparse Cholesky: unknown ordering " + std::to_string(ordering));
+  if (ordering == CSE_SPARSE_ORDERING_GIVEN && !permutation)
+    return CseFail(CSE_ERR_INVALID, "sparse Cholesky: the given ordering without a permutation");
+  try {
+    SparseCholeskyPlan P;
+    const size_t n = (size_t)N;
+    P.num_block_rows = N;
+    P.num_input_blocks = row_begin[N];
+    P.in_row_begin.assign(row_begin, row_begin + N + 1);
+    P.in_block_col.assign(block_col, block_col + P.num_input_blocks);
+    // The order.
+    P.position.assign(n, -1);
+    if (ordering == CSE_SPARSE_ORDERING_MINIMUM_DEGREE) {
+      if ((rc = SparseCholeskyMinimumDegree(N, row_begin, block_col, &P.permutation))) return rc;
+    } else {
+      P.permutation.resize(n);
+      for (size_t k = 0; k < n; ++k)
+        P.permutation[k] = ordering == CSE_SPARSE_ORDERING_GIVEN ? permutation[k] : (int32_t)k;
+    }
+    for (size_t k = 0; k < n; ++k) {
+      const int32_t r = P.permutation[k];
+      if (r < 0 || r >= N || P.position[(size_t)r] >= 0)
+        return CseFail(CSE_ERR_INVALID, "sparse Cholesky: the given order is not a permutation of the block rows");
+      P.position[(size_t)r] = (int32_t)k;
+    }
+    // The input's transposed index, and B's strict lower triangle by columns.
+    P.in_col_begin.assign(n + 1, 0);
+    std::vector<int64_t> a_begin(n + 1, 0);
+    for (int64_t r = 0; r < N; ++r)
+      for (int64_t k = row_begin[r] + 1; k < row_begin[r + 1]; ++k) {
+        ++P.in_col_begin[(size_t)block_col[k] + 1];
+        ++a_begin[(size_t)std::min(P.position[(size_t)r], P.position[(size_t)block_col[k]]) + 1];
+      }
+    for (size_t c = 0; c < n; ++c) P.in_col_begin[c + 1] += P.in_col_begin[c], a_begin[c + 1] += a_begin[c];
+    P.in_col_block.resize((size_t)(P.num_input_blocks - N));
+    P.in_col_row.resize(P.in_col_block.size());
+    std::vector<int32_t> a_rows(P.in_col_block.size());
+    {
+      std::vector<int64_t> fill(P.in_col_begin.begin(), P.in_col_begin.end() - 1);
+      std::vector<int64_t> afill(a_begin.begin(), a_begin.end() - 1);
+      for (int64_t r = 0; r < N; ++r)
+        for (int64_t k = row_begin[r] + 1; k < row_begin[r + 1]; ++k) {
+          const int32_t c = block_col[k];
+          const int64_t at = fill[(size_t)c]++;
+          P.in_col_block[(size_t)at] = (int32_t)k, P.in_col_row[(size_t)at] = (int32_t)r;
+          const int32_t p = P.position[(size_t)r], q = P.position[(size_t)c];
+          a_rows[(size_t)afill[(size_t)std::min(p, q)]++] = std::max(p, q);
+        }
+    }
+    // Column structures with fill, the elimination tree and its levels:
+    // struct(j) = B's column j below the diagonal, and struct(c) \ {j} of every
+    // child c; parent(j) = min struct(j).
+    P.parent.assign(n, -1);
+    P.level.assign(n, 0);
+    P.col_begin.assign(n + 1, 0);
+    std::vector<int32_t> col_rows, child_head(n, -1), child_next(n, -1), mark(n, -1);
+    for (int64_t j = 0; j < N; ++j) {
+      const size_t begin = col_rows.size();
+      for (int64_t k = a_begin[(size_t)j]; k < a_begin[(size_t)j + 1]; ++k) {
+        const int32_t i = a_rows[(size_t)k];
+        if (mark[(size_t)i] != j) mark[(size_t)i] = (int32_t)j, col_rows.push_back(i);
+      }
+      for (int32_t c = child_head[(size_t)j]; c >= 0; c = child_next[(size_t)c])
+        for (int64_t k = P.col_begin[(size_t)c]; k < P.col_begin[(size_t)c + 1]; ++k) {
+          const int32_t i = col_rows[(size_t)k];
+          if (i != j && mark[(size_t)i] != j) mark[(size_t)i] = (int32_t)j, col_rows.push_back(i);
+        }
+      std::sort(col_rows.begin() + (std::ptrdiff_t)begin, col_rows.end());
+      P.col_begin[(size_t)j + 1] = (int64_t)col_rows.size();
+      if ((int64_t)col_rows.size() + N >= INT32_MAX)
+        return CseFail(CSE_ERR_UNSUPPORTED, "sparse Cholesky: 2^31 or more factor blocks");
+      if (col_rows.size() > begin) {
+        const int32_t p = col_rows[begin];
+        P.parent[(size_t)j] = p;
+        child_next[(size_t)j] = child_head[(size_t)p], child_head[(size_t)p] = (int32_t)j;
+        P.level[(size_t)p] = std::max(P.level[(size_t)p], P.level[(size_t)j] + 1);
+      }
+      const int64_t m = (int64_t)(col_rows.size() - begin);
+      P.num_block_products += m * (m + 1) / 2;
+    }
+    P.num_factor_blocks = (int64_t)col_rows.size() + N;
+    // L by rows: a row's columns ascend because the columns are walked in order.
+    P.row_begin.assign(n + 1, 0);
+    for (int32_t i : col_rows) ++P.row_begin[(size_t)i + 1];
+    for (size_t i = 0; i < n; ++i) P.row_begin[i + 1] += P.row_begin[i] + 1;
+    P.block_col.resize((size_t)P.num_factor_blocks);
+    P.block_row.resize((size_t)P.num_factor_blocks);
+    P.col_block.resize(col_rows.size());
+    {
+      std::vector<int64_t> fill(P.row_begin.begin(), P.row_begin.end() - 1);
+      for (int64_t j = 0; j < N; ++j)
+        for (int64_t k = P.col_begin[(size_t)j]; k < P.col_begin[(size_t)j + 1]; ++k) {
+          const int32_t i = col_rows[(size_t)k];
+          const int64_t id = fill[(size_t)i]++;
+          P.block_col[(size_t)id] = (int32_t)j, P.block_row[(size_t)id] = i;
+          P.col_block[(size_t)k] = (int32_t)id;
+        }
+      for (int64_t i = 0; i < N; ++i) {
+        const int64_t id = P.row_begin[(size_t)i + 1] - 1;
+        P.block_col[(size_t)id] = P.block_row[(size_t)id] = (int32_t)i;
+      }
+    }
+    // Scatter and its inverse.
+    P.scatter.resize((size_t)P.num_input_blocks);
+    P.source.assign((size_t)P.num_factor_blocks, -1);
+    for (int64_t r = 0; r < N; ++r)
+      for (int64_t k = row_begin[r]; k < row_begin[r + 1]; ++k) {
+        const int32_t p = P.position[(size_t)r], q = P.position[(size_t)block_col[k]];
+        const int32_t i = std::max(p, q), j = std::min(p, q);
+        const int32_t* first = &P.block_col[(size_t)P.row_begin[(size_t)i]];
+        const int32_t* last = &P.block_col[(size_t)P.row_begin[(size_t)i + 1] - 1] + 1;
+        const int64_t id = P.row_begin[(size_t)i] + (std::lower_bound(first, last, j) - first);
+        const bool transposed = p < q;
+        P.scatter[(size_t)k] = transposed ? ~(int32_t)id : (int32_t)id;
+        P.source[(size_t)id] = transposed ? -2 - (int32_t)k : (int32_t)k;
+      }
+    // The level table.
+    for (size_t j = 0; j < n; ++j) P.num_levels = std::max(P.num_levels, P.level[j] + 1);
+    P.level_begin.assign((size_t)P.num_levels + 1, 0);
+    P.target_begin.assign((size_t)P.num_levels + 1, 0);
+    for (size_t j = 0; j < n; ++j) {
+      ++P.level_begin[(size_t)P.level[j] + 1];
+      P.target_begin[(size_t)P.level[j] + 1] += P.col_begin[j + 1] - P.col_begin[j];
+    }
+    for (int32_t l = 0; l < P.num_levels; ++l) {
+      P.max_level_columns = std::max<int64_t>(P.max_level_columns, P.level_begin[(size_t)l + 1]);
+      P.level_begin[(size_t)l + 1] += P.level_begin[(size_t)l];
+      P.target_begin[(size_t)l + 1] += P.target_begin[(size_t)l];
+    }
+    P.level_columns.resize(n);
+    P.level_targets.resize(col_rows.size());
+    {
+      std::vector<int64_t> fill(P.level_begin.begin(), P.level_begin.end() - 1);
+      std::vector<int64_t> tfill(P.target_begin.begin(), P.target_begin.end() - 1);
+      for (int64_t j = 0; j < N; ++j) {
+        const size_t l = (size_t)P.level[(size_t)j];
+        P.level_columns[(size_t)fill[l]++] = (int32_t)j;
+        for (int64_t k = P.col_begin[(size_t)j]; k < P.col_begin[(size_t)j + 1]; ++k)
+          P.level_targets[(size_t)tfill[l]++] = P.col_block[(size_t)k];
+      }
+    }
+    // Device bytes: the tables, L and the inverses of its diagonal blocks,
+    // the two solve vectors, the per-column status words and info.
+    const int64_t nf = P.num_factor_blocks, ni = P.num_input_blocks;
+    P.device_bytes = 4 * (2 * N)                     // permutation, position
+                     + 8 * 2 * (N + 1) + 4 * (2 * nf + (nf - N) + nf)  // row/col begin, block col/row, col_block, source
+                     + 4 * (N + (nf - N))            // level columns, level targets
+                     + 8 * 2 * (N + 1) + 4 * (ni + 2 * (ni - N))       // the input's arrays
+                     + 8 * 81 * (nf + N) + 8 * 2 * 9 * N + 4 * (N + 1);
+    *plan = std::move(P);
+  } catch (const std::bad_alloc&) {
+    return CseFail(CSE_ERR_OOM, "sparse Cholesky plan: host allocation failed");
+  }
+  return CSE_OK;
+}
+
 }  // namespace cse

@@ -540,6 +540,71 @@ constexpr DenseCholeskyTile DenseCholeskyTrailingTile(int64_t R, int64_t x, int6
 // CSE_ERR_INVALID: n < 1 or an unknown precision.
 int PlanDenseCholesky(int64_t n, int32_t precision, DenseCholeskyPlan* plan);
 
+// ---- The block-sparse Cholesky factorization (cse_sparse_cholesky_*): the
+// SparseCholesky behind SPARSE_SCHUR (sparse_cholesky.h:72-113), a supernode =
+// one 9 x 9 block column.  The input is the upper triangle A(r, c), r <= c, as
+// block-compressed rows (PlanSchurSparse's format).  With B = P A P^T and
+// permutation[k] = the original block row at position k, L's block (i, j),
+// i >= j, starts from B(i, j): the input block (permutation[j], permutation[i])
+// transposed, or (permutation[i], permutation[j]) as it is.
+//
+// The factorization is left-looking by levels of the elimination tree: every
+// block of column j reads columns on lower levels only, so one level's columns
+// are independent.  A level launches the diagonal kernel over its columns and
+// the target kernel over its off-diagonal blocks; a solve launches one kernel
+// a level forward and one backward.
+struct SparseCholeskyCounts {
+  int64_t num_block_rows = 0, num_input_blocks = 0, num_factor_blocks = 0;
+  // sum over columns k of m_k (m_k + 1) / 2, m_k = the blocks of column k below
+  // its diagonal: the 9 x 9 x 9 products of one factorization.
+  int64_t num_block_products = 0;
+  int64_t device_bytes = 0;
+  int32_t num_levels = 0, max_level_columns = 0;
+};
+struct SparseCholeskyPlan : SparseCholeskyCounts {
+  std::vector<int32_t> permutation, position;  // position = the inverse
+  // L by block rows in the permuted order: row i is [row_begin[i],
+  // row_begin[i + 1]), columns ascending, the diagonal last.
+  std::vector<int64_t> row_begin;  // [N + 1]
+  std::vector<int32_t> block_col, block_row;  // [num_factor_blocks]
+  // The column index: the blocks of column j below the diagonal, rows ascending.
+  std::vector<int64_t> col_begin;  // [N + 1]
+  std::vector<int32_t> col_block;  // [num_factor_blocks - N]
+  std::vector<int32_t> parent, level;  // [N]; parent -1 at a root
+  // Scatter: input block b lands in L's block scatter[b] as it is, or, when
+  // scatter[b] is negative, in block ~scatter[b] transposed.  source is the
+  // inverse by L's blocks: input block source[t] >= 0 as it is, -1 = fill,
+  // source[t] <= -2 = input block -2 - source[t] transposed.  Both hold every
+  // index below 2^31 - 1.
+  std::vector<int32_t> scatter;  // [num_input_blocks]
+  std::vector<int32_t> source;   // [num_factor_blocks]
+  // The level table: level l's columns are level_columns[level_begin[l] ..
+  // level_begin[l + 1]) ascending, its off-diagonal target blocks
+  // level_targets[target_begin[l] .. target_begin[l + 1]) ascending.
+  std::vector<int64_t> level_begin, target_begin;  // [num_levels + 1]
+  std::vector<int32_t> level_columns;              // [N]
+  std::vector<int32_t> level_targets;              // [num_factor_blocks - N]
+  // The input's own arrays and its transposed index (the refinement's
+  // residual reads the lower half through it): the blocks of column c above
+  // the diagonal are in_col_block[in_col_begin[c] ..), of rows in_col_row, ascending.
+  std::vector<int64_t> in_row_begin, in_col_begin;  // [N + 1]
+  std::vector<int32_t> in_block_col;                // [num_input_blocks]
+  std::vector<int32_t> in_col_block, in_col_row;    // [num_input_blocks - N]
+};
+// The greedy minimum-degree order: repeatedly the block row with the fewest
+// uneliminated neighbours in the elimination graph (fill edges included), the
+// lowest index on ties; once the remaining graph is a clique the rest follows
+// in index order.  Bit rows: N^2 / 8 bytes of host memory.
+int SparseCholeskyMinimumDegree(int64_t N, const int64_t* row_begin, const int32_t* block_col,
+                                std::vector<int32_t>* permutation);
+// ordering: CSE_SPARSE_ORDERING_*; permutation is read with GIVEN only.
+// CSE_ERR_INVALID: null pointers, N < 1, a row without its leading diagonal,
+// columns not ascending or out of range, a GIVEN array that is no permutation,
+// an unknown ordering.  CSE_ERR_UNSUPPORTED: 2^31 or more factor blocks (or
+// 9 N + 1 beyond int32).  CSE_ERR_OOM.
+int PlanSparseCholesky(int64_t N, const int64_t* row_begin, const int32_t* block_col, int32_t ordering,
+                       const int32_t* permutation, SparseCholeskyPlan* plan);
+
 }  // namespace cse
 
 #endif  // CSE_PLAN_HPP_

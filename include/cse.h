@@ -960,6 +960,97 @@ int cse_dense_cholesky_info(cse_evaluator* ev, int32_t* info);
  * refinement vectors of :543-592); allocates nothing, needs no evaluator. */
 int cse_dense_cholesky_workspace(int64_t n, int32_t precision, int64_t* device_bytes);
 
+/* ---- Block-sparse Cholesky on the device ---------------------------------
+ * The SparseCholesky behind SPARSE_SCHUR: SparseSchurComplementSolver::
+ * SolveReducedLinearSystem (internal/ceres/schur_complement_solver.cc:290-333)
+ * hands BlockRandomAccessSparseMatrix's cells to a SparseCholesky
+ * (sparse_cholesky.h:72-113) whose symbolic analysis is done once, every later
+ * Factorize having the same structure (sparse_cholesky.h:55-56), wrapped in
+ * RefinedSparseCholesky when max_num_refinement_iterations > 0
+ * (sparse_cholesky.h:119).  No vendor library: a host-only symbolic plan, then
+ * a left-looking factorization of 9 x 9 blocks in HIP, one level of the
+ * elimination tree at a time, the block products on the matrix cores.  The
+ * evaluator supplies the device and the stream and owns the tables, L and the
+ * solve vectors; nothing here needs a Schur-eligible program, the matrix is
+ * the caller's.  Factorize and solve are asynchronous on the evaluator's
+ * stream (no host wait), use no atomics on floating-point data and are
+ * bit-identical from run to run.  CSE_ERR_UNSUPPORTED on a cse_create_multi
+ * handle. */
+enum { CSE_SPARSE_ORDERING_NATURAL = 0, CSE_SPARSE_ORDERING_MINIMUM_DEGREE = 1, CSE_SPARSE_ORDERING_GIVEN = 2 };
+typedef struct cse_sparse_cholesky_summary {
+  int64_t num_block_rows, num_input_blocks, num_factor_blocks, num_block_products;
+  int64_t device_bytes;             /* tables + factor values + per-solve vectors */
+  int32_t num_levels, max_level_columns;
+} cse_sparse_cholesky_summary;
+
+/* The symbolic analysis (sparse_cholesky.h:55-56: once per structure).  The
+ * upper triangle of a symmetric matrix of 9 x 9 blocks as block-compressed
+ * rows, host arrays, exactly what cse_schur_complement_sparse_structure
+ * returns: block k of row r, k in [row_begin[r], row_begin[r + 1]), is
+ * A(r, block_col[k]); every row starts with its diagonal block and block_col
+ * ascends.  ordering: NATURAL, the identity; MINIMUM_DEGREE, the greedy rule
+ * (repeatedly the block row with the fewest uneliminated neighbours in the
+ * elimination graph, fill edges included, the lowest index on ties; it stands
+ * where the reference's linear_solver_ordering_type AMD does and is not
+ * SuiteSparse's AMD); GIVEN, permutation[k] = the original block row placed at
+ * position k (ignored otherwise, may then be NULL).  Builds the elimination
+ * tree, L's block structure with fill and the level tables on the host and
+ * uploads them; a second analyze replaces the first and drops its factor.
+ * num_block_products is the sum over columns of m (m + 1) / 2, m = the
+ * column's blocks below its diagonal.  summary may be NULL.  CSE_ERR_INVALID:
+ * null pointers, a row without its leading diagonal, columns not ascending or
+ * out of range, a GIVEN array that is not a permutation, an unknown ordering.
+ * CSE_ERR_UNSUPPORTED: 2^31 or more factor blocks.  CSE_ERR_OOM.  Value
+ * offsets are 64-bit throughout. */
+int cse_sparse_cholesky_analyze(cse_evaluator* ev, int64_t num_block_rows, const int64_t* row_begin,
+                                const int32_t* block_col, int32_t ordering, const int32_t* permutation,
+                                cse_sparse_cholesky_summary* summary);
+
+/* Host copies of what the analysis decided; any pointer may be NULL.
+ * permutation [num_block_rows]; L's block rows in the permuted order,
+ * factor_row_begin [num_block_rows + 1] and factor_block_col
+ * [num_factor_blocks], a row's columns ascending and its diagonal last; the
+ * elimination tree's parent, -1 at a root; each column's level, 0 at a leaf,
+ * else 1 + the largest level of a child: every column that column j reads
+ * lies on a lower level.  CSE_ERR_INVALID before any analyze. */
+int cse_sparse_cholesky_structure(cse_evaluator* ev, int32_t* permutation, int64_t* factor_row_begin,
+                                  int32_t* factor_block_col, int32_t* parent, int32_t* level);
+
+/* SparseCholesky::Factorize (sparse_cholesky.h:72-113).  d_values:
+ * [num_input_blocks][9][9] row-major as cse_schur_complement_sparse writes
+ * them (diagonal blocks whole and symmetric); read only.  It is bound as
+ * cse_schur_init binds the Jacobian: a refining solve reads it again.  L goes
+ * into storage the evaluator owns, allocated by the first factorize after an
+ * analyze, kept for the later ones and released by the next analyze or by
+ * cse_destroy.  A pivot that is not positive and finite
+ * (LinearSolverTerminationType::FAILURE, schur_complement_solver.cc:316-321)
+ * shows in cse_sparse_cholesky_info; the evaluator's status word and cse_wait
+ * are not affected.  CSE_ERR_INVALID: a null pointer, no prior analyze. */
+int cse_sparse_cholesky_factorize(cse_evaluator* ev, const double* d_values);
+
+/* L's values, [num_factor_blocks][9][9] row-major in cse_sparse_cholesky_
+ * structure's order, copied to d_L on the stream; a diagonal block's strict
+ * upper triangle is zero.  CSE_ERR_INVALID: null, no prior factorize. */
+int cse_sparse_cholesky_factor_values(cse_evaluator* ev, double* d_L);
+
+/* SparseCholesky::Solve (schur_complement_solver.cc:323-331; one "iteration",
+ * :329): x = A^-1 rhs in the original order, 9 num_block_rows entries each,
+ * the same buffer or disjoint.  max_num_refinement_iterations > 0 is
+ * RefinedSparseCholesky (sparse_cholesky.h:119), SparseIterativeRefiner's
+ * loop: that many times r = rhs - A x in FP64 from d_values, x += L^-T L^-1 r;
+ * d_values must therefore stay unchanged until the last refining solve.  After
+ * a failed factorization x is assigned zeros.  CSE_ERR_INVALID: a null
+ * pointer, no prior factorize, a negative count, partial overlap. */
+int cse_sparse_cholesky_solve(cse_evaluator* ev, const double* d_rhs, double* d_x,
+                              int32_t max_num_refinement_iterations);
+
+/* Waits on the stream; 0 after a success, else 1 + the smallest permuted
+ * scalar column whose pivot failed: a column fed NaN by a failed descendant
+ * has a larger index than that descendant, so this is what a sequential
+ * factorization in the permuted order reports.  A later factorize starts again
+ * from 0.  CSE_ERR_INVALID before any factorize. */
+int cse_sparse_cholesky_info(cse_evaluator* ev, int32_t* info);
+
 /* ---- One host solve, several GPUs --------------------------------------
  * The reference evaluates on one device (ContextImpl's single stream,
  * include/ceres/internal/cuda_buffer.h:98) and Ceres' host solve calls one
